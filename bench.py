@@ -9,9 +9,16 @@ face-crops/sec forward+backward at per-GPU batch 512).
 One step = zero_grad + forward + multi-task loss + backward + fused clip/Adam step of
 NetworkWithPointHead("mobilenetv1") with the training script's default flags (landmark head on) on one
 synthetic batch that is already resident in HBM (+ the RCCL gradient all-reduce, overlapped with
-backward, when N > 1; weak scaling: 512 crops per GPU).  The optimiser step is INSIDE `value`;
-`optimizer_ms` reports it alone for reference.  `--backbone resnet18` / `--batch 256` time BASELINE
-configs 3 and 2 the same way.  Prints ONE JSON line on rank 0.
+backward, when N > 1; weak scaling: 512 crops per GPU).  The optimiser step is INSIDE `value`.
+Every step starts from the seeded initial weights, copied back in front of it (WeightReset), so that
+the same arguments give the same computation on every run.
+`--backbone resnet18` / `--batch 256` time BASELINE configs 3 and 2 the same way.  Prints ONE JSON
+line on rank 0.
+
+A plain run only sets up, warms up, times `--steps` steps and prints the line.  `--full` adds, after
+the timed region, the per-kernel roofline pass, `optimizer_ms` (the optimiser step alone), the
+communication diagnostics (N > 1), the two extra legs, the copy probe and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -50,28 +57,34 @@ def parse():
                     help="fp32 (default, the headline) | bf16-compute = BASELINE config 5's bf16 leg (separate line, dtype bf16; mobilenetv1 only): activations "
                     "and gradients bf16 in 64-channel blocks, pointwise convolutions as ONE bf16 MFMA product with fp32 accumulation (csrc/bc_*.hip).  The "
                     "storage-only variants bf16 / bf16-all of earlier rounds are retired and raise")
-    ap.add_argument("--no-legs", action="store_true", help="skip the two short extra legs the default N = 1 run appends to its line (`legs`: batch 256 fp32 = "
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline, after its timed region: the per-kernel "
+                    "roofline pass, the optimiser step alone, the communication diagnostics (N > 1), the two extra legs, the copy probe and the CPU "
+                    "baseline (each can be skipped with its --no-* option).  Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / "
+                    "float64): the loss, the per-sample task losses, and the parameters, gradients and float buffers of the network after the "
+                    "optimiser step; at most 64 MB in all (larger arrays are replaced by a fixed seeded sample)")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the two short extra legs the default N = 1 run appends to its line (`legs`: batch 256 fp32 = "
                     "BASELINE config 2, batch 512 bf16-compute = config 5's bf16 leg; 10 steps each after the headline is measured)")
-    ap.add_argument("--traffic-json", default=None, help="rocprofv3 PMC summary (tools/pmc_summary.py) taken with THIS build; "
+    ap.add_argument("--traffic-json", default=None, help="--full: rocprofv3 PMC summary (tools/pmc_summary.py) taken with THIS build; "
                     "fills roofline.traffic (null without it)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI (the measurement); gloo with --share-gpu: "
                     "a dry run of the multi-rank code path on a one-GPU box (tests/test_bench_dp_dryrun_gpu.py) - its rate is not a result")
     ap.add_argument("--share-gpu", action="store_true", help="dry run: every rank uses device 0")
-    ap.add_argument("--comm-only", action="store_true", help="N > 1: time ONLY the bucketed in-place gradient all-reduce of one step (the buckets a real "
+    ap.add_argument("--comm-only", action="store_true", help="--full, N > 1: time ONLY the bucketed in-place gradient all-reduce of one step (the buckets a real "
                     "backward announces, replayed on buffers of the same sizes): ms per step and bus bandwidth, no compute beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-copy-probe", action="store_true", help="skip the same-process streaming probe (copy_probe object)")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the per-call HIP-event instrumentation (roofline = null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-copy-probe", action="store_true", help="--full: skip the same-process streaming probe (copy_probe object)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: skip the per-call HIP-event instrumentation (roofline = null)")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every kernel from Python instead of replaying one captured hipGraph")
     ap.add_argument("--force-graph", action="store_true", help="always replay the captured hipGraph (default at N=1: whichever of graph replay "
                     "and eager enqueue the warm-up measures faster)")
     ap.add_argument("--serial-streams", action="store_true",
                     help="(kept for old command lines; every kernel of a step already runs on one stream - the weight-gradient side stream of earlier "
                     "rounds is an experiment hook that is off)")
-    ap.add_argument("--per-call", action="store_true", help="print the roofline pass call by call (kernel, shape, us, GB/s, TFLOP/s) on stderr")
-    ap.add_argument("--cpu-batch", type=int, default=64)
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="time budget of the CPU baseline sample")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = min(host cores, 32)")
+    ap.add_argument("--per-call", action="store_true", help="--full: print the roofline pass call by call (kernel, shape, us, GB/s, TFLOP/s) on stderr")
+    ap.add_argument("--cpu-batch", type=int, default=64, help="--full: the CPU baseline's small batch")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time budget of the CPU baseline sample")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: CPU baseline threads, 0 = min(host cores, 32)")
     return ap.parse_args()
 
 
@@ -397,8 +410,78 @@ def cpu_baseline(args):
                       f"{small['batch']} ({small['value']:.1f} crops/s); fp32, torch CPU kernels, {n} of the host's {os.cpu_count()} hardware threads"}
 
 
+class WeightReset:
+    """Copies the seeded initial parameters back in front of every step, so that every step starts from the same weights.  Without it
+    each step would continue from the weights the previous one left: the weight-gradient reductions add in no fixed order (atomics), and
+    after tens of Adam steps on one batch two runs with the same arguments computed visibly different steps.  Adam's moments and the
+    BatchNorm running statistics are left to run on: with the weights fixed they are running averages of the same gradients and batch
+    statistics, which converge instead of drifting apart.  One ttk_multi_copy launch per 32 parameters (3 for the default network, 13 MB
+    read and written), argument arrays built once."""
+
+    def __init__(self, params):
+        from ctypes import c_int64, c_void_p
+
+        import trackertraincode._hip as H
+
+        self.lib, self._keep = H.lib(), [p.detach().clone() for p in params]
+        for p in params:
+            assert p.dtype == torch.float32 and p.is_contiguous()
+        self.launches = []
+        for i in range(0, len(params), 32):
+            src, dst = self._keep[i:i + 32], params[i:i + 32]
+            n = len(dst)
+            self.launches.append((n, (c_void_p * n)(*[H.ptr(a) for a in src]), (c_void_p * n)(*[H.ptr(b) for b in dst]),
+                                  (c_int64 * n)(*[b.numel() for b in dst])))
+
+    def __call__(self):
+        for args in self.launches:
+            self.lib.call("ttk_multi_copy", *args)
+
+
+DUMP_BYTES = 63_000_000  # --dump-outputs: array data in all (with the .npy headers under 64 MB)
+
+
+def dump_outputs(out_dir, out, net):
+    """What the last timed step computed, as a caller of the step receives it: the loss and the per-sample task losses it returns, and the
+    parameters, gradients and floating-point buffers (BatchNorm statistics) it left in the network.  float64 stays float64, every other
+    dtype is written as float32.  If the whole exceeds DUMP_BYTES, every array of more than 2^20 elements is replaced by the same fixed,
+    seeded sample of its elements (flattened, indices ascending) - the same arguments give the same files on every run."""
+    import re
+    import zlib
+
+    import numpy as np
+
+    arrays = {"loss": out["loss"]}
+    arrays.update({f"mt_loss.{k}": v for k, v in out["mt_losses"].items()})
+    for name, p in net.named_parameters():
+        arrays[f"param.{name}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad
+    arrays.update({f"buffer.{name}": b for name, b in net.named_buffers() if b.is_floating_point()})
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[re.sub(r"[^A-Za-z0-9_.-]", "_", k)] = v.cpu().numpy() if v.dtype == torch.float64 else v.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        big = {k for k, a in host.items() if a.size > (1 << 20)}
+        small = sum(a.nbytes for k, a in host.items() if k not in big)
+        frac = (DUMP_BYTES - small) / sum(host[k].nbytes for k in big)
+        for k in big:
+            a = host[k].reshape(-1)
+            rng = np.random.default_rng(zlib.crc32(k.encode()))
+            host[k] = a[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full and (args.comm_only or args.per_call or args.traffic_json):
+        raise SystemExit("--comm-only, --per-call and --traffic-json belong to the --full measurements: add --full")
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -431,6 +514,7 @@ def main():
         parallel.install(reducer)            # gradient arenas are all-reduced in place while backward continues
         opt.grad_scale = reducer.grad_scale  # 1/world, applied inside the fused clip+Adam kernel
     params = list(net.parameters())
+    reset = WeightReset(params)  # every step starts from the same weights (what each step computes is the same on every run)
 
     graphed = train.GraphedTrainStep(net, crit, opt) if (world == 1 and not args.no_graph) else None
 
@@ -442,7 +526,7 @@ def main():
         if reducer is not None:
             reducer.finish(params)
         opt.step()  # fused global-norm clip + Adam (2 launches, no host sync)
-        return out["loss"]
+        return out
 
     use_graph = [graphed is not None]
 
@@ -450,8 +534,9 @@ def main():
         # single GPU: the whole step (zero_grad, forward, losses, backward, clip+Adam) can be one captured hipGraph that
         # is replayed - same kernels, one enqueue call instead of ~200; data-parallel runs stay eager (RCCL calls
         # are issued from Python between backward and the optimiser)
+        reset()
         if use_graph[0] and not timer.enabled:
-            return graphed.run(batches, 0)["loss"]
+            return graphed.run(batches, 0)  # (the graph's static outputs: overwritten by the next replay)
         return eager_step()
 
     def sync():
@@ -468,8 +553,8 @@ def main():
     if graphed is not None and not args.force_graph:
         # Both enqueue modes run the same kernels.  Replay removes the host from the loop; eager enqueue lets the
         # launch-ahead queue hide the gaps between the ~200 small dependent kernels.  Which one wins depends on the host:
-        # measure both during warm-up (untimed, runs as long as the timed region) and use the faster.
-        probe = {}
+        # measure both during warm-up (untimed, as long as the timed region up to 20 steps) and use the faster.
+        probe, probe_steps = {}, min(max(args.steps, 4), 20)
         for mode in (False, True):  # eager first: it then runs exactly as it would without any capture in the process
             use_graph[0] = mode
             try:
@@ -477,10 +562,10 @@ def main():
                     step()
                 sync()
                 tp = time.perf_counter()
-                for _ in range(max(args.steps, 4)):
+                for _ in range(probe_steps):
                     step()
                 sync()
-                probe[mode] = (time.perf_counter() - tp) / max(args.steps, 4) * 1e3
+                probe[mode] = (time.perf_counter() - tp) / probe_steps * 1e3
             except Exception as exc:  # a failed capture must not cost the measurement: eager enqueue always works
                 if not mode:
                     raise
@@ -505,7 +590,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        out = step()
     host_enqueue = time.perf_counter() - t0  # host time to ENQUEUE the steps (no sync yet)
     sync()
     elapsed = time.perf_counter() - t0
@@ -513,9 +598,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    loss = float(out["loss"].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, net)  # before anything else runs a step: the last timed step's results
+    del out
     # Per-kernel pass for the roofline object: the same step again with HIP events around every conv C-ABI call (one stream, as in the timed
     # region).  It is a separate pass because the events cost ~3 ms/step of host time, which would distort `value`.
-    roof_steps = 0 if args.no_kernel_timing else min(args.steps, 10)
+    roof_steps = 0 if (args.no_kernel_timing or not args.full) else min(args.steps, 10)
     if roof_steps:
         use_side = MB._USE_WGRAD_STREAM
         MB._USE_WGRAD_STREAM = False
@@ -531,7 +620,7 @@ def main():
     # reducer exchanged, the device time of the collectives (they overlap backward), and the EXPOSED time - from the end of backward's last
     # kernel to the completion of the last collective, i.e. how long the optimiser waited for the exchange; max over the ranks.
     comm = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         try:  # (diagnostics only: `value` is already measured - a failure here must not cost the line)
             ranks = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
             dist.all_gather(ranks, torch.tensor([rank], dtype=torch.int64, device=device))
@@ -575,12 +664,14 @@ def main():
             reducer.measure = False
             comm = {"error": f"{type(e).__name__}: {e}"[:300]}
     # optimiser step alone (already inside `value`; reported for reference)
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(5):
-        opt.step()
-    sync()
-    opt_ms = (time.perf_counter() - t1) / 5 * 1e3
+    opt_ms = None
+    if args.full:
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(5):
+            opt.step()
+        sync()
+        opt_ms = (time.perf_counter() - t1) / 5 * 1e3
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -657,7 +748,7 @@ def main():
                                   else {"fp32_mfma_frac_of_157TF": per_gpu * ALGO_FLOP_PER_CROP / (PEAK_FP32_MFMA_TFLOPS * 1e12)})} if args.backbone == "mobilenetv1"
                               else {"fp32_mfma_frac_of_157TF": per_gpu * 4.203e9 / (PEAK_FP32_MFMA_TFLOPS * 1e12)}),  # 4.203 GFLOP/crop
             "enqueue": ("hipGraph replay (1 capture)" if use_graph[0] else "eager Python launches") + enqueue_note,
-            "optimizer_ms": opt_ms, "host_enqueue_ms_per_step": host_enqueue / args.steps * 1e3, "loss": float(loss.item()),
+            "optimizer_ms": opt_ms, "host_enqueue_ms_per_step": host_enqueue / args.steps * 1e3, "loss": loss,
             "kernels_ms_per_step": {k: round(v["ms_per_step"], 3) for k, v in sorted(ks.items(), key=lambda kv: -kv[1]["ms"])},
             "gemm_family_TFLOPs": (sum(v["flops"] for k, v in ks.items() if k.startswith("pw")) /
                                    max(sum(v["ms"] for k, v in ks.items() if k.startswith("pw")) * 1e-3, 1e-12) / 1e12) if ks else None,
@@ -665,7 +756,7 @@ def main():
         }
         if comm is not None:
             line["comm"] = comm
-        if world == 1 and default_run and not args.no_legs:
+        if world == 1 and default_run and args.full and not args.no_legs:
             # BASELINE configs 2 and 5 on the same clock as the headline: two short legs in this process, AFTER the headline
             # fields above are final; they never change `value`
             legs = {}
@@ -677,9 +768,9 @@ def main():
             legs["note"] = ("same process, after the timed region: B256 = BASELINE config 2 (fp32, batch 256), bf16_compute = config 5's bf16 leg (batch 512); "
                             "10 timed steps each after 3 warm-up steps, the whole step (optimiser inside) replayed as one hipGraph")
             line["legs"] = legs
-        if world == 1 and not args.no_copy_probe:
+        if world == 1 and args.full and not args.no_copy_probe:
             line["copy_probe"] = copy_probe(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(line))
     if world > 1:

@@ -18,7 +18,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_sharing_the_gpu(extra):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29571",
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "64", "--dist-backend", "gloo", "--share-gpu",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "64", "--dist-backend", "gloo", "--share-gpu",
            "--no-cpu-baseline", "--no-copy-probe", *extra]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

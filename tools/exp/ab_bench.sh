@@ -4,7 +4,7 @@ O=$1; shift; mkdir -p $O
 for rep in 1 2; do
   for v in "$@"; do
     lib=$PWD/neuralnet-tracker-traincode_amd/libttk_hip.so; [ $v != base ] && lib=$PWD/tools/exp/_build/libttk_$v.so
-    TTK_LIB=$lib python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    TTK_LIB=$lib python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels_ms_per_step']
