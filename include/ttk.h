@@ -24,6 +24,11 @@
  *    pixels x 128 bytes; over channels-last rows the same kernels touched 128-byte pieces of 4C-byte rows and streamed 10-20 %
  *    slower (profiles/r03_stream_sweep.txt).  These tensors only travel from kernel to kernel; ttk_bn_act hands out a plain
  *    channels-last copy (MobileNet's intermediate feature maps), ttk_avgpool_fwd the [B][C] features.
+ *    Channel counts that are not multiples of 32 (the width-scaled backbones, ttk_anyc_* below; C a multiple of 8) keep blocks of 32 and
+ *    end with ONE narrower block:  [M][32], ..., [M][32], [M][C mod 32];  element (m, c) of block b = c >> 5 lies at
+ *        b * M * 32 + m * width(b) + (c & 31),   width(b) = min(32, C - 32 b).
+ *    For C a multiple of 32 this IS the layout above; C = 8, 16 and 24 are plain channels-last rows.  One network therefore mixes the two
+ *    kernel families layer by layer without a conversion.
  *    The ResNet18 entry points (ttk_conv_*, ttk_stem7_*, ttk_maxpool_*, ttk_bn_add_act, ttk_bn_bwd_apply) keep channels-last rows
  *    y[n][h][w][c]; ttk_avgpool_* serve both (TTK_LAYOUT_ROWS).
  *  - training-mode BatchNorm is split in three: the producing conv writes its RAW output y and
@@ -49,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 28
+#define TTK_ABI_VERSION 29
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -257,6 +262,47 @@ int ttk_avgpool_bwd(const float* gfeat, const void* y, float* bn, const void* sk
  * MobileNet.forward returns, mobilenet_v1.py:165-186).  y, skip: channel blocks; a: plain channels-last rows. */
 int ttk_bn_act(const float* y, const float* bn, const float* skip, float* a, int64_t rows, int C,
                ttk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The ANY-CHANNEL-COUNT family (csrc/anyc_*.hip): the MobileNet path for channel counts that are multiples of 8 in 8..2048 -
+ * MobileNet(widen_factor=w), reference backbones/mobilenet_v1.py:113-146.  Each entry point follows the contract of the tuned
+ * entry point it stands in for (same reference lines, same apply-on-load BatchNorm forms, same partial sums, TTK_AUX_GMAX raised by
+ * every producer of a gradient), on the layout with a narrower last block (see "Activation layout"), fp32 storage only.  Differences:
+ *  - the pointwise products run on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32) from the RAW weights w[Cout][Cin]: no
+ *    prepared operand, no operand bounds (row TTK_BN_AUX is not read);
+ *  - no float atomics: every weight gradient is stored as workgroup / slice rows in caller-provided scratch and folded in a fixed
+ *    order inside the entry point (bitwise reproducible in every mode).  dw is overwritten (accumulate == 0) or added to;
+ *  - part rows: ttk_anyc_partial_rows(pixels) for the stem (output pixels), ttk_anyc_dw_fwd (output pixels), ttk_anyc_dw_bwd_data
+ *    (input pixels) and ttk_anyc_avgpool_bwd (B * HW); ttk_partial_rows_gemm(M) for ttk_anyc_pw_fwd / ttk_anyc_pw_bwd_data.
+ * The tuned entry points keep their domains and refusals.
+ * ------------------------------------------------------------------------------------------- */
+int ttk_anyc_partial_rows(int64_t pixels);
+int ttk_anyc_stem_fwd(const float* x, const float* w, float* y, float* part, const float* pivot, int B, int H, int W, int Cout,
+                      ttk_stream_t stream);
+size_t ttk_anyc_stem_wgrad_scratch_bytes(int B, int H, int W, int Cout);
+int ttk_anyc_stem_bwd_weight(const float* g, const float* y, const float* bn, const float* x, float* dw, int accumulate, float* scratch, int B,
+                             int H, int W, int Cout, ttk_stream_t stream);
+/* a_out needs stride 1 (only blocks with a residual connection materialise their input).  The BlurPool pair is two launches with
+ * different weights, as with ttk_dwconv3x3_fwd. */
+int ttk_anyc_dw_fwd(const float* yprev, const float* bn_prev, const float* skip_prev, float* a_out, const float* w, float* y, float* part,
+                    const float* pivot, int B, int H, int W, int C, int stride, ttk_stream_t stream);
+/* dw (nullable): the fused weight gradient dW[C][9]; then dw_scratch of ttk_anyc_dw_wgrad_scratch_bytes(B, H, W, C) bytes. */
+size_t ttk_anyc_dw_wgrad_scratch_bytes(int B, int H, int W, int C);
+int ttk_anyc_dw_bwd_data(const float* g_dw, const float* y_dw, const float* bn_dw, const float* w, const float* skip_grad, const float* yprev,
+                         float* bn_prev, const float* skip_prev, const float* a_in, float* g_prev, float* part, float* dw, int dw_accumulate,
+                         float* dw_scratch, int B, int H, int W, int C, int stride, ttk_stream_t stream);
+int ttk_anyc_pw_fwd(const float* ydw, const float* bn_dw, const float* w, float* y, float* part, const float* pivot, int64_t M, int Cin, int Cout,
+                    ttk_stream_t stream);
+/* w is the weight as is ([Cout][Cin]; no transposed copy).  Raises bn_dw[TTK_BN_AUX][TTK_AUX_GMAX] to max |g_dw|. */
+int ttk_anyc_pw_bwd_data(const float* g, const float* y, const float* bn_pw, const float* w, const float* ydw, float* bn_dw, float* g_dw,
+                         float* part, int64_t M, int Cin, int Cout, ttk_stream_t stream);
+size_t ttk_anyc_pw_wgrad_scratch_bytes(int64_t M, int Cin, int Cout);
+int ttk_anyc_pw_bwd_weight(const float* g, const float* y, const float* bn_pw, const float* ydw, const float* bn_dw, float* dw, int accumulate,
+                           float* scratch, int64_t M, int Cin, int Cout, ttk_stream_t stream);
+int ttk_anyc_avgpool_fwd(const float* y, const float* bn, const float* skip, float* feat, int B, int HW, int C, ttk_stream_t stream);
+int ttk_anyc_avgpool_bwd(const float* gfeat, const float* y, float* bn, const float* skip, float* g, float* part, int B, int HW, int C,
+                         ttk_stream_t stream);
+int ttk_anyc_bn_act(const float* y, const float* bn, const float* skip, float* a, int64_t rows, int C, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The bf16-COMPUTE path of the MobileNet backbone (`--precision bf16-compute`, BASELINE config 5's bf16 leg; csrc/bc_*.hip).  The

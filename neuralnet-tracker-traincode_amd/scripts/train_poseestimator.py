@@ -109,9 +109,13 @@ def setup_losses(args, net):
 
 
 def create_net(args):
+    backbone_args = {"use_blurpool": args.with_blurpool}
+    widen_factor = float(getattr(args, "widen_factor", 1.0))
+    if widen_factor != 1.0:  # (at the default the key stays out of the saved config, as in checkpoints written so far)
+        backbone_args["widen_factor"] = widen_factor
     return models.NetworkWithPointHead(
         enable_point_head=args.with_pointhead, enable_face_detector=False, config=args.backbone,
-        enable_uncertainty=args.with_nll_loss, backbone_args={"use_blurpool": args.with_blurpool}, enable_6drot=args.enable_6drot,
+        enable_uncertainty=args.with_nll_loss, backbone_args=backbone_args, enable_6drot=args.enable_6drot,
     )
 
 
@@ -167,6 +171,9 @@ def make_parser():
                    help="fp32 (the reference's precision) | bf16-compute (mobilenetv1): activations and their gradients bfloat16 in 64-channel blocks AND bf16 "
                    "operands of the pointwise convolutions (one MFMA product, fp32 accumulation; master weights, statistics and Adam fp32).  The "
                    "storage-only variants bf16 / bf16-all of earlier rounds are retired (they were slower than fp32): they raise, naming bf16-compute")
+    p.add_argument("--widen-factor", default=1.0, type=float, dest="widen_factor",
+                   help="mobilenetv1: width multiplier of the backbone (the reference's MobileNet(widen_factor=...)): every channel count becomes "
+                   "int(c * factor) and must be a multiple of 8 in 8..2048 - 0.25, 0.5, 0.75, 1.0, 1.5, 2.0; fp32 precision only")
     p.add_argument("--graph-steps", default=False, action="store_true",
                    help="single GPU: replay one captured hipGraph per training step instead of ~150 eager launches (train.GraphedTrainStep)")
     return p

@@ -108,9 +108,20 @@ _SIGNATURES = {
     "ttk_bc_avgpool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
     "ttk_bc_dw_bwd_data": [_P] * 12 + [_I, _P] + [_I] * 5,
     "ttk_bc_bn_bwd_finalize_fold": [_P, _I, _I, _L, _P, _P, _P, _P, _I, _P, _I, _L, _P, _I],
+    # any-channel-count family (csrc/anyc_*.hip): width-scaled MobileNet backbones
+    "ttk_anyc_stem_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I],
+    "ttk_anyc_stem_bwd_weight": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I],
+    "ttk_anyc_dw_fwd": [_P] * 8 + [_I] * 5,
+    "ttk_anyc_dw_bwd_data": [_P] * 12 + [_I, _P] + [_I] * 5,
+    "ttk_anyc_pw_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I],
+    "ttk_anyc_pw_bwd_data": [_P] * 8 + [_L, _I, _I],
+    "ttk_anyc_pw_bwd_weight": [_P] * 6 + [_I, _P, _L, _I, _I],
+    "ttk_anyc_avgpool_fwd": [_P, _P, _P, _P, _I, _I, _I],
+    "ttk_anyc_avgpool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
+    "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 # Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the
@@ -182,6 +193,10 @@ class _Library:
         self.cdll.ttk_bc_pw_bwd_fused_rows.argtypes, self.cdll.ttk_bc_pw_bwd_fused_rows.restype = [c_int64, c_int, c_int], c_int
         self.cdll.ttk_bc_pw_wgrad_slices.argtypes, self.cdll.ttk_bc_pw_wgrad_slices.restype = [c_int64, c_int, c_int], c_int
         self.cdll.ttk_bc_pw_bwd_fused_scratch_bytes.argtypes, self.cdll.ttk_bc_pw_bwd_fused_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
+        self.cdll.ttk_anyc_partial_rows.argtypes, self.cdll.ttk_anyc_partial_rows.restype = [c_int64], c_int
+        self.cdll.ttk_anyc_stem_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_stem_wgrad_scratch_bytes.restype = [c_int] * 4, ctypes.c_size_t
+        self.cdll.ttk_anyc_dw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_dw_wgrad_scratch_bytes.restype = [c_int] * 4, ctypes.c_size_t
+        self.cdll.ttk_anyc_pw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_pw_wgrad_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
         self._fns = {}
         self._stale_reported = False
         for name, sig in _SIGNATURES.items():
@@ -290,6 +305,16 @@ class _Library:
             self.call("ttk_multi_copy", n, (c_void_p * n)(*[ptr(a) for a in s]), (c_void_p * n)(*[ptr(b) for b in d]),
                       (c_int64 * n)(*[b.numel() for b in d]))
 
+    @functools.lru_cache(maxsize=None)
+    def anyc_partial_rows(self, pixels: int) -> int:
+        """Rows of partial sums the pixel-wise kernels of the any-channel-count family write for `pixels` pixels."""
+        return self.cdll.ttk_anyc_partial_rows(pixels)
+
+    @functools.lru_cache(maxsize=None)
+    def anyc_wgrad_scratch_bytes(self, kind: str, *shape) -> int:
+        """Scratch bytes of a weight gradient of the any-channel-count family: kind "stem" (B, H, W, Cout), "dw" (B, H, W, C), "pw" (M, Cin, Cout)."""
+        return getattr(self.cdll, f"ttk_anyc_{kind}_wgrad_scratch_bytes")(*shape)
+
     # (pure functions of their integer arguments, asked ~80 times per step: cached)
     @functools.lru_cache(maxsize=None)
     def partial_rows_elementwise(self, items: int) -> int:
@@ -368,6 +393,32 @@ def to_blocks(t: torch.Tensor) -> torch.Tensor:
     return t.reshape(-1, C // CHANNEL_BLOCK, CHANNEL_BLOCK).transpose(0, 1).contiguous().view(t.shape)
 
 
+def to_blocks_any(t: torch.Tensor) -> torch.Tensor:
+    """`to_blocks` for any channel count (include/ttk.h, "Activation layout"): blocks of 32 and one narrower last block,
+    [M][32], ..., [M][32], [M][C mod 32].  Equal to `to_blocks` for C a multiple of 32; plain rows for C < 32."""
+    C = t.shape[-1]
+    if C % CHANNEL_BLOCK == 0:
+        return to_blocks(t)
+    full = C // CHANNEL_BLOCK * CHANNEL_BLOCK
+    rows = t.reshape(-1, C)
+    parts = [to_blocks(rows[:, :full]).reshape(-1)] if full else []
+    return torch.cat(parts + [rows[:, full:].reshape(-1)]).view(t.shape)
+
+
+def from_blocks_any(t: torch.Tensor) -> torch.Tensor:
+    """Inverse of `to_blocks_any`."""
+    C = t.shape[-1]
+    if C % CHANNEL_BLOCK == 0:
+        return from_blocks(t)
+    full = C // CHANNEL_BLOCK * CHANNEL_BLOCK
+    flat = t.reshape(-1)
+    M = flat.numel() // C
+    tail = flat[M * full:].view(M, C - full)
+    if not full:
+        return tail.reshape(t.shape)
+    return torch.cat([from_blocks(flat[:M * full].view(M, full)), tail], dim=1).reshape(t.shape)
+
+
 def from_blocks(t: torch.Tensor) -> torch.Tensor:
     """Inverse of `to_blocks`: a tensor whose memory holds channel blocks -> the channels-last values, same nominal shape."""
     C = t.shape[-1]
@@ -400,4 +451,5 @@ def exported_symbols() -> list[str]:
             "ttk_pwconv_wgrad_partial_bytes", "ttk_pwconv_wgrad_scratch_bytes", "ttk_stem_wgrad_partial_bytes", "ttk_conv_wgrad_partial_bytes", "ttk_stem7_wgrad_partial_bytes",
             "ttk_pwconv1x1_bwd_fused_rows", "ttk_pwconv1x1_bwd_fused_partial_bytes", "ttk_bc_prepared_bytes", "ttk_bc_partial_rows_pw",
             "ttk_bc_partial_rows_dw", "ttk_bc_partial_rows_pool", "ttk_bc_pw_wgrad_scratch_bytes", "ttk_bc_pw_bwd_fused_rows",
-            "ttk_bc_pw_bwd_fused_scratch_bytes", "ttk_bc_pw_wgrad_slices"] + list(_SIGNATURES)
+            "ttk_bc_pw_bwd_fused_scratch_bytes", "ttk_bc_pw_wgrad_slices", "ttk_anyc_partial_rows", "ttk_anyc_stem_wgrad_scratch_bytes",
+            "ttk_anyc_dw_wgrad_scratch_bytes", "ttk_anyc_pw_wgrad_scratch_bytes"] + list(_SIGNATURES)

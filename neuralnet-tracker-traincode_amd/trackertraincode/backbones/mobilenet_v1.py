@@ -48,6 +48,25 @@ _BLOCKS = (
     ("dw6", 1024, 1024, 1),
 )
 _INTERMEDIATES = ("dw2_1", "dw3_1", "dw4_1", "dw5_5", "dw6")
+_STEM_CHANNELS = 32
+
+
+def _scaled_blocks(widen_factor):
+    """(stem channels, block table) of MobileNet(widen_factor): every channel count truncated as the reference does, int(c * widen_factor)
+    (reference mobilenet_v1.py:113-146).  The HIP kernels take multiples of 8 in 8..2048; anything else raises ValueError."""
+    def ch(c):
+        v = int(c * widen_factor)
+        if v < 8 or v > 2048 or v % 8:
+            raise ValueError(f"widen_factor={widen_factor} gives a channel count int({c} * {widen_factor}) = {v}; the HIP backbone takes "
+                             "multiples of 8 in 8..2048 (e.g. widen_factor 0.25, 0.5, 0.75, 1.0, 1.5, 2.0)")
+        return v
+    return ch(_STEM_CHANNELS), tuple((name, ch(cin), ch(cout), stride) for name, cin, cout, stride in _BLOCKS)
+
+
+def _tuned_c(c) -> bool:
+    """Channel counts of the tuned kernels (ttk_dwconv3x3_*, ttk_pwconv1x1_*, ttk_avgpool_*, ttk_bn_act): powers of two in 32..1024.
+    Every other count runs on the any-channel-count family (ttk_anyc_*, include/ttk.h)."""
+    return 32 <= c <= 1024 and (c & (c - 1)) == 0
 
 
 class DepthWiseBlock(nn.Module):
@@ -152,27 +171,36 @@ class _Stage(NamedTuple):
     skip: torch.Tensor | None  # residual input added before the ReLU of this stage's output
 
 
-def _part_buffer(B, H, W, device, blur=False):
+def _part_buffer(B, H, W, device, blur=False, blocks=_BLOCKS, c0=_STEM_CHANNELS):
     """One scratch buffer large enough for every layer's [rows][2][C] partial sums."""
     L = _hip.lib()
     need = 0
     h = (H + 1) // 2
-    need = max(need, L.partial_rows_elementwise(B * h * h * 8) * 2 * 32)
-    for _, cin, cout, stride in _BLOCKS:
+    need = max(need, (L.partial_rows_elementwise(B * h * h * 8) if c0 == _STEM_CHANNELS else L.anyc_partial_rows(B * h * h)) * 2 * c0)
+    for _, cin, cout, stride in blocks:
         ho = (h - 1) // stride + 1
-        need = max(need, L.partial_rows_dwconv(B, h, h, cin, stride, True) * 2 * cin)     # dw bwd-data
-        need = max(need, L.partial_rows_dwconv(B, h, h, cin, stride, False) * 2 * cin)    # dw fwd
-        if blur and stride == 2:  # the stride-1 depthwise conv behind the blur
-            need = max(need, L.partial_rows_dwconv(B, ho, ho, cin, 1, False) * 2 * cin, L.partial_rows_dwconv(B, ho, ho, cin, 1, True) * 2 * cin)
-        need = max(need, L.partial_rows_gemm(B * ho * ho, cin, cout) * 2 * cout, L.partial_rows_gemm(B * ho * ho, cout, cin, True) * 2 * cin)  # pw fwd / bwd-data
-        need = max(need, L.partial_rows_elementwise(B * ho * ho * (cout // 4)) * 2 * cout)  # pool bwd
+        if _tuned_c(cin):
+            need = max(need, L.partial_rows_dwconv(B, h, h, cin, stride, True) * 2 * cin)     # dw bwd-data
+            need = max(need, L.partial_rows_dwconv(B, h, h, cin, stride, False) * 2 * cin)    # dw fwd
+            if blur and stride == 2:  # the stride-1 depthwise conv behind the blur
+                need = max(need, L.partial_rows_dwconv(B, ho, ho, cin, 1, False) * 2 * cin, L.partial_rows_dwconv(B, ho, ho, cin, 1, True) * 2 * cin)
+        else:  # (the family's rows depend on the pixel count alone: the input's covers forward, backward and the pair behind a blur)
+            need = max(need, L.anyc_partial_rows(B * h * h) * 2 * cin)
+        if _tuned_c(cin) and _tuned_c(cout):
+            need = max(need, L.partial_rows_gemm(B * ho * ho, cin, cout) * 2 * cout, L.partial_rows_gemm(B * ho * ho, cout, cin, True) * 2 * cin)  # pw fwd / bwd-data
+        else:
+            need = max(need, L.partial_rows_gemm(B * ho * ho) * 2 * max(cin, cout))
+        if _tuned_c(cout):
+            need = max(need, L.partial_rows_elementwise(B * ho * ho * (cout // 4)) * 2 * cout)  # pool bwd
+        else:
+            need = max(need, L.anyc_partial_rows(B * ho * ho) * 2 * cout)
         h = ho
     return torch.empty(need, dtype=torch.float32, device=device)
 
 
 class _Ctx:
     """Everything one forward pass leaves behind for its backward."""
-    __slots__ = ("x", "stages", "a_in", "part", "dims", "pool_skip", "wparams", "HW", "B", "prep", "bf", "gdt", "frozen", "blur")
+    __slots__ = ("x", "stages", "a_in", "part", "dims", "pool_skip", "wparams", "HW", "B", "prep", "bf", "gdt", "frozen", "blur", "blocks")
 
 
 _IDENTITY_BN: dict = {}
@@ -191,13 +219,15 @@ def _identity_bn(C, device):
     return _IDENTITY_BN[key].clone()
 
 
-def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blur=None):
+def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blur=None, blocks=_BLOCKS):
     """Launches the forward kernels.  `params`: flat list [conv1.w, bn1.w, bn1.b, (dw.w, bn_dw.w,
     bn_dw.b, pw.w, bn_sep.w, bn_sep.b) x 13]; `buffers`: flat list of (running_mean, running_var,
     num_batches_tracked) per BN in the same order; `blur`: per block, the BlurPool2D kernel as a depthwise weight
-    [Cin,1,3,3] (use_blurpool, strided blocks) or None."""
+    [Cin,1,3,3] (use_blurpool, strided blocks) or None; `blocks`: the instance's (width-scaled) block table.  Per layer, a shape the
+    tuned kernels accept runs on them; every other layer runs on the any-channel-count family (ttk_anyc_*) - same contracts, same layout."""
     L = _hip.lib()
-    blur = list(blur) if blur is not None else [None] * len(_BLOCKS)
+    blur = list(blur) if blur is not None else [None] * len(blocks)
+    c0 = params[0].shape[0]
     _hip.check_tensors([x], "input")  # what came from outside is checked once; everything else below is allocated here
     _hip.check_tensors(params, "parameter")
     _hip.check_tensors(buffers, "BatchNorm buffer")
@@ -206,16 +236,16 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
     dev = x.device
     B, _, H, W = x.shape
     Ho, Wo = (H + 1) // 2, (W + 1) // 2
-    part = _part_buffer(B, H, W, dev, any(b is not None for b in blur))
+    part = _part_buffer(B, H, W, dev, any(b is not None for b in blur), blocks, c0)
     ctx = _Ctx()
-    ctx.x, ctx.part, ctx.B = x, part, B
+    ctx.x, ctx.part, ctx.B, ctx.blocks = x, part, B, blocks
     ctx.blur = []
     ctx.frozen = frozen  # backward through eval-mode BatchNorm: the fixed affine map (ttk_bn_bwd_frozen)
     ctx.stages, ctx.a_in, ctx.dims = [], [], []
     act_dtype = torch.float32
     bf = 0  # TTK_STORE_* bits of the C-ABI: fp32 tensors (the bf16 storage variants under these kernels are retired)
     ctx.bf, ctx.gdt = bf, torch.float32
-    bns = _BnArena([32] + [c for _, cin, cout, _ in _BLOCKS for c in (cin, cout)], dev)
+    bns = _BnArena([c0] + [c for _, cin, cout, _ in blocks for c in (cin, cout)], dev)
 
     def pivot(bi):
         """The statistics pivot of BatchNorm `bi` (include/ttk.h): its running mean - the producer sums y - pivot, the finalisation adds
@@ -236,21 +266,37 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
 
     part_arg = p(part)
     # forward and data-gradient weight operands of all 13 pointwise convs, one launch
-    w_pws = [params[3 + 6 * k + 3] for k in range(len(_BLOCKS))]
-    sizes = [L.pwconv_prepared_bytes(cin, cout) for _, cin, cout, _ in _BLOCKS]
-    pool = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
-    ctx.prep = list(torch.split(pool, sizes))
-    L.pwconv_prepare_weights(w_pws, ctx.prep)
+    # (the tuned pointwise layers; the any-channel-count GEMMs read the raw weights)
+    tuned_pw = [k for k, (_, cin, cout, _) in enumerate(blocks) if _tuned_c(cin) and _tuned_c(cout)]
+    ctx.prep = [None] * len(blocks)
+    if tuned_pw:
+        sizes = [L.pwconv_prepared_bytes(blocks[k][1], blocks[k][2]) for k in tuned_pw]
+        pool = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        for k, t in zip(tuned_pw, torch.split(pool, sizes)):
+            ctx.prep[k] = t
+        L.pwconv_prepare_weights([params[3 + 6 * k + 3] for k in tuned_pw], [ctx.prep[k] for k in tuned_pw])
     # ---- stem (reference :122-126,161-163)
-    y0 = torch.empty((B, Ho, Wo, 32), dtype=act_dtype, device=dev)
-    L.call("ttk_stem_fwd", p(x), p(params[0]), p(y0), part_arg, pivot(0), B, H, W, bf)
-    bn = bns.take(32)
-    finalize(bn, L.partial_rows_elementwise(B * Ho * Wo * 8), 32, B * Ho * Wo, params[1], params[2], 0)
+    y0 = torch.empty((B, Ho, Wo, c0), dtype=act_dtype, device=dev)
+    bn = bns.take(c0)
+    if c0 == _STEM_CHANNELS:
+        L.call("ttk_stem_fwd", p(x), p(params[0]), p(y0), part_arg, pivot(0), B, H, W, bf)
+        finalize(bn, L.partial_rows_elementwise(B * Ho * Wo * 8), 32, B * Ho * Wo, params[1], params[2], 0)
+    else:
+        L.call("ttk_anyc_stem_fwd", p(x), p(params[0]), p(y0), part_arg, pivot(0), B, H, W, c0)
+        finalize(bn, L.anyc_partial_rows(B * Ho * Wo), c0, B * Ho * Wo, params[1], params[2], 0)
     prev = _Stage(y0, bn, None)
     ctx.stages.append(prev)
     h, w_ = Ho, Wo
     pi, bi = 3, 1
-    for name, cin, cout, stride in _BLOCKS:
+    def dw_fwd(yprev, bn_prev, skip_prev, a_out, w, y, pv, hh, ww, C, stride):
+        """One depthwise launch -> the rows of partial sums it wrote."""
+        if _tuned_c(C):
+            L.call("ttk_dwconv3x3_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride, bf)
+            return L.partial_rows_dwconv(B, hh, ww, C, stride, False)
+        L.call("ttk_anyc_dw_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride)
+        return L.anyc_partial_rows(B * ((hh - 1) // stride + 1) * ((ww - 1) // stride + 1))
+
+    for name, cin, cout, stride in blocks:
         w_dw, g_dw, b_dw, w_pw, g_pw, b_pw = params[pi:pi + 6]
         pi += 6
         has_skip = stride == 1 and cin == cout
@@ -263,15 +309,12 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
             # same depthwise kernel; the blurred tensor crosses HBM once with the identity constant block (its partial sums
             # are written to the scratch rows and overwritten by the next launch)
             t = torch.empty((B, ho, wo, cin), dtype=act_dtype, device=dev)
-            L.call("ttk_dwconv3x3_fwd", p(prev.y), p(prev.bn), p(prev.skip), None, p(blur[k]), p(t), part_arg, None, B, h, w_, cin, stride, bf)
+            dw_fwd(prev.y, prev.bn, prev.skip, None, blur[k], t, None, h, w_, cin, stride)
             st_t = _Stage(t, _identity_bn(cin, dev), None)
-            L.call("ttk_dwconv3x3_fwd", p(t), p(st_t.bn), None, None, p(w_dw), p(ydw), part_arg, pivot(bi), B, ho, wo, cin, 1, bf)
-            dw_rows = L.partial_rows_dwconv(B, ho, wo, cin, 1, False)
+            dw_rows = dw_fwd(t, st_t.bn, None, None, w_dw, ydw, pivot(bi), ho, wo, cin, 1)
             ctx.blur.append((st_t, blur[k]))
         else:
-            L.call("ttk_dwconv3x3_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(a_in), p(w_dw), p(ydw), part_arg, pivot(bi), B, h, w_, cin,
-                   stride, bf)
-            dw_rows = L.partial_rows_dwconv(B, h, w_, cin, stride, False)
+            dw_rows = dw_fwd(prev.y, prev.bn, prev.skip, a_in, w_dw, ydw, pivot(bi), h, w_, cin, stride)
             ctx.blur.append(None)
         if _EXP_TENSOR_HOOK is not None:
             _EXP_TENSOR_HOOK("y", k, ydw)
@@ -279,11 +322,16 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
         finalize(bn_dw, dw_rows, cin, B * ho * wo, g_dw, b_dw, bi)
         ypw = torch.empty((B, ho, wo, cout), dtype=act_dtype, device=dev)
         M = B * ho * wo
-        L.call("ttk_pwconv1x1_fwd", p(ydw), p(bn_dw), None, p(ypw), part_arg, pivot(bi + 1), M, cin, cout, p(ctx.prep[len(ctx.dims)]), bf)
+        if ctx.prep[k] is not None:
+            L.call("ttk_pwconv1x1_fwd", p(ydw), p(bn_dw), None, p(ypw), part_arg, pivot(bi + 1), M, cin, cout, p(ctx.prep[k]), bf)
+            pw_rows = L.partial_rows_gemm(M, cin, cout)
+        else:
+            L.call("ttk_anyc_pw_fwd", p(ydw), p(bn_dw), p(w_pw), p(ypw), part_arg, pivot(bi + 1), M, cin, cout)
+            pw_rows = L.partial_rows_gemm(M)
         if _EXP_TENSOR_HOOK is not None:
             _EXP_TENSOR_HOOK("y", k, ypw)
         bn_pw = bns.take(cout)
-        finalize(bn_pw, L.partial_rows_gemm(M, cin, cout), cout, M, g_pw, b_pw, bi + 1)
+        finalize(bn_pw, pw_rows, cout, M, g_pw, b_pw, bi + 1)
         bi += 2
         ctx.stages.append(_Stage(ydw, bn_dw, None))
         prev = _Stage(ypw, bn_pw, a_in)
@@ -293,7 +341,10 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
         h, w_ = ho, wo
     C = prev.y.shape[-1]
     feat = torch.empty((B, C), dtype=torch.float32, device=dev)
-    L.call("ttk_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C, bf)
+    if _tuned_c(C):
+        L.call("ttk_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C, bf)
+    else:
+        L.call("ttk_anyc_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C)
     ctx.HW = h * w_
     return feat, ctx
 
@@ -340,7 +391,7 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
     _hip.check_tensors([gfeat], "gradient")
     _hip.check_tensors(params, "parameter")
     p = _hip.fast_ptr
-    B, part, bf = ctx.B, ctx.part, ctx.bf
+    B, part, bf, blocks = ctx.B, ctx.part, ctx.bf, ctx.blocks
     # one zeroed arena for every parameter gradient (the weight-gradient kernels accumulate atomically): one fill launch
     offs, total = [], 0
     for q in params:
@@ -364,38 +415,56 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
         L.call("ttk_bn_bwd_finalize", p(part), rows, Cc, count, p(params[gi]), p(stage.bn), p(grads[gi]), p(grads[gi + 1]), 0)
 
     main = torch.cuda.current_stream(gfeat.device)
-    side = _side_stream(gfeat.device) if (_USE_WGRAD_STREAM and not _DETERMINISTIC) else None
+    side = _side_stream(gfeat.device) if (_USE_WGRAD_STREAM and not _DETERMINISTIC and all(q is not None for q in ctx.prep)) else None
     wg_scratch = None
     if _DETERMINISTIC:
         # one scratch buffer for every weight-gradient reduction of this backward (used one after the other on one stream):
         # slices / workgroups store partial results there and a second kernel folds them in a fixed order
-        need = max(L.pwconv_wgrad_partial_bytes(B * d[2] * d[3], d[4], d[5]) for d in ctx.dims)
+        pw_dims = [d for d in ctx.dims if _tuned_c(d[4]) and _tuned_c(d[5])]
+        dw_dims = [(d, bl) for d, bl in zip(ctx.dims, ctx.blur) if _tuned_c(d[4])]
+        need = max([L.pwconv_wgrad_partial_bytes(B * d[2] * d[3], d[4], d[5]) for d in pw_dims] + [0])
         need = max(need, L.cdll.ttk_stem_wgrad_partial_bytes())
-        need = max(need, max(L.cdll.ttk_pwconv1x1_bwd_fused_partial_bytes(B * d[2] * d[3], d[4], d[5]) for d in ctx.dims))
-        need = max(need, max(L.partial_rows_dwconv(B, d[0], d[1], d[4], d[6], True) * 9 * d[4] * 4 for d in ctx.dims))
-        need = max([need] + [L.partial_rows_dwconv(B, d[2], d[3], d[4], 1, True) * 9 * d[4] * 4 for d, bl in zip(ctx.dims, ctx.blur) if bl is not None])
+        need = max([need] + [L.cdll.ttk_pwconv1x1_bwd_fused_partial_bytes(B * d[2] * d[3], d[4], d[5]) for d in pw_dims])
+        need = max([need] + [L.partial_rows_dwconv(B, d[0], d[1], d[4], d[6], True) * 9 * d[4] * 4 for d, _ in dw_dims])
+        need = max([need] + [L.partial_rows_dwconv(B, d[2], d[3], d[4], 1, True) * 9 * d[4] * 4 for d, bl in dw_dims if bl is not None])
         wg_scratch = torch.empty(need // 4, dtype=torch.float32, device=gfeat.device)
     # the weight gradient of the wide pointwise layers (Cin, Cout multiples of 256) always reduces slice partials in a fixed order
     # (csrc/pwconv_r.hip: faster than float atomics for 256 x 256 tiles): its scratch, in every mode
-    pw_need = max([L.pwconv_wgrad_scratch_bytes(B * d[2] * d[3], d[4], d[5]) for d in ctx.dims] + [0])
+    pw_need = max([L.pwconv_wgrad_scratch_bytes(B * d[2] * d[3], d[4], d[5]) for d in ctx.dims if _tuned_c(d[4]) and _tuned_c(d[5])] + [0])
     pw_scratch = wg_scratch if (wg_scratch is not None and wg_scratch.numel() * 4 >= pw_need) else (
         torch.empty(pw_need // 4, dtype=torch.float32, device=gfeat.device) if pw_need else None)
     keep = []
     # The fused depthwise weight gradient of the fp32 kernels: workgroup rows (see _DW_WGRAD_ROWS above; deterministic mode: rows + a fixed-order fold of its own).
     # (the BlurPool blocks and frozen fine-tuning keep float atomics unless deterministic: they pass `wg_scratch`, not these rows)
     dw_rows = wg_scratch
-    rows_layers = [d for d, bl in zip(ctx.dims, ctx.blur) if bl is None]
+    rows_layers = [d for d, bl in zip(ctx.dims, ctx.blur) if bl is None and _tuned_c(d[4])]
     if dw_rows is None and _DW_WGRAD_ROWS and not ctx.frozen and rows_layers:
         need = max(L.partial_rows_dwconv(B, d[0], d[1], d[4], d[6], True) * 9 * d[4] for d in rows_layers)
         dw_rows = torch.empty(need, dtype=torch.float32, device=gfeat.device)
 
-    g = torch.empty(last.y.shape, dtype=ctx.gdt, device=last.y.device)
-    L.call("ttk_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C, bf)
-    bwd_finalize(last, L.partial_rows_elementwise(B * ctx.HW * (C // 4)), B * ctx.HW, len(params) - 2)
-    if _EXP_TENSOR_HOOK is not None:
-        _EXP_TENSOR_HOOK("g", len(_BLOCKS), g)
+    # The any-channel-count layers (width-scaled backbones): ONE scratch buffer for their weight gradients - workgroup / slice rows that
+    # the entry points fold in a fixed order (no atomics in that family, in any mode); used by one launch after the other on this stream.
+    _, _, H, W = ctx.x.shape
+    c0 = ctx.stages[0].y.shape[-1]
+    any_need = 0 if c0 == _STEM_CHANNELS else L.anyc_wgrad_scratch_bytes("stem", B, H, W, c0)
+    for d, bl in zip(ctx.dims, ctx.blur):
+        if not _tuned_c(d[4]):
+            any_need = max(any_need, L.anyc_wgrad_scratch_bytes("dw", B, d[2], d[3], d[4]) if bl is not None else L.anyc_wgrad_scratch_bytes("dw", B, d[0], d[1], d[4]))
+        if not (_tuned_c(d[4]) and _tuned_c(d[5])):
+            any_need = max(any_need, L.anyc_wgrad_scratch_bytes("pw", B * d[2] * d[3], d[4], d[5]))
+    any_scratch = torch.empty(any_need // 4, dtype=torch.float32, device=gfeat.device) if any_need else None
 
-    for k in range(len(_BLOCKS) - 1, -1, -1):
+    g = torch.empty(last.y.shape, dtype=ctx.gdt, device=last.y.device)
+    if _tuned_c(C):
+        L.call("ttk_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C, bf)
+        bwd_finalize(last, L.partial_rows_elementwise(B * ctx.HW * (C // 4)), B * ctx.HW, len(params) - 2)
+    else:
+        L.call("ttk_anyc_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C)
+        bwd_finalize(last, L.anyc_partial_rows(B * ctx.HW), B * ctx.HW, len(params) - 2)
+    if _EXP_TENSOR_HOOK is not None:
+        _EXP_TENSOR_HOOK("g", len(blocks), g)
+
+    for k in range(len(blocks) - 1, -1, -1):
         h, w_, ho, wo, cin, cout, stride, has_skip = ctx.dims[k]
         pi = 3 + 6 * k
         w_dw, w_pw = params[pi], params[pi + 3]
@@ -407,8 +476,16 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
         # tail (too few tiles left for 256 CUs) and the HBM-bound depthwise kernels fill each other's gaps.
         dW = grads[pi + 3]
         g_dw = torch.empty(st_dw.y.shape, dtype=ctx.gdt, device=st_dw.y.device)
-        fused_rows = L.cdll.ttk_pwconv1x1_bwd_fused_rows(M, cin, cout) if (_FUSED_PW_BWD and bf == 0) else 0  # (one kernel for both gradients: main stream, with or without the side stream)
-        if fused_rows:
+        pw_tuned = ctx.prep[k] is not None
+        fused_rows = L.cdll.ttk_pwconv1x1_bwd_fused_rows(M, cin, cout) if (_FUSED_PW_BWD and bf == 0 and pw_tuned) else 0  # (one kernel for both gradients: main stream, with or without the side stream)
+        if not pw_tuned:
+            # any-channel-count layer: exact-fp32 MFMA GEMMs from the raw weights; the weight gradient is slice rows + a fixed-order fold
+            L.call("ttk_anyc_pw_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), p(dW), 0, p(any_scratch), M, cin, cout)
+            L.call("ttk_anyc_pw_bwd_data", p(g), p(st_pw.y), p(st_pw.bn), p(w_pw), p(st_dw.y), p(st_dw.bn), p(g_dw), p(part), M, cin, cout)
+            bwd_finalize(st_dw, L.partial_rows_gemm(M), M, pi + 1)
+            if _EXP_TENSOR_HOOK is not None:
+                _EXP_TENSOR_HOOK("g", k, g_dw)
+        elif fused_rows:
             # the first three pointwise layers (HBM-bound, the largest activations): weight and data gradient in ONE kernel - g,
             # the conv output and the depthwise output are read once instead of twice (csrc/pw_bwd_fused.hip)
             L.call("ttk_pwconv1x1_bwd_fused", p(g), p(st_pw.y), p(st_pw.bn), p(w_pw), p(ctx.prep[k]), p(st_dw.y), p(st_dw.bn), p(g_dw), p(dW),
@@ -430,7 +507,7 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
         else:
             L.call("ttk_pwconv1x1_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), p(dW),
                    p(wg_scratch) if wg_scratch is not None else (p(pw_scratch) if L.pwconv_wgrad_scratch_bytes(M, cin, cout) else None), M, cin, cout, bf)
-        if not fused_rows:
+        if pw_tuned and not fused_rows:
             L.call("ttk_pwconv1x1_bwd_data", p(g), p(st_pw.y), p(st_pw.bn), None, p(st_dw.y), p(st_dw.bn), p(g_dw), p(part), M,
                    cin, cout, p(ctx.prep[k]), bf)
             bwd_finalize(st_dw, L.partial_rows_gemm(M, cout, cin, True), M, pi + 1)
@@ -439,7 +516,22 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
         # -- depthwise: weight gradient, then data gradient (+ residual gradient, + producer's bn sums)
         dWd = grads[pi]  # accumulated by the fused weight-gradient path of bwd_data
         g_prev = torch.empty(st_prev.y.shape, dtype=ctx.gdt, device=st_prev.y.device)
-        if ctx.blur[k] is not None:
+        gi_prev = pi - 2 if k > 0 else 1
+        if not _tuned_c(cin):
+            # any-channel-count layer (BlurPool blocks: the same two steps as below)
+            if ctx.blur[k] is not None:
+                st_t, w_blur = ctx.blur[k]
+                g_t = torch.empty(st_t.y.shape, dtype=ctx.gdt, device=st_t.y.device)
+                L.call("ttk_anyc_dw_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), None, p(st_t.y), p(st_t.bn), None, None, p(g_t),
+                       p(part), p(dWd), 0, p(any_scratch), B, ho, wo, cin, 1)
+                L.call("ttk_bn_bwd_frozen", p(st_t.bn), cin)
+                L.call("ttk_anyc_dw_bwd_data", p(g_t), p(st_t.y), p(st_t.bn), p(w_blur), None, p(st_prev.y), p(st_prev.bn), p(st_prev.skip),
+                       None, p(g_prev), p(part), None, 0, None, B, h, w_, cin, stride)
+            else:
+                L.call("ttk_anyc_dw_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), p(g) if has_skip else None, p(st_prev.y),
+                       p(st_prev.bn), p(st_prev.skip), p(a_in), p(g_prev), p(part), p(dWd), 0, p(any_scratch), B, h, w_, cin, stride)
+            bwd_finalize(st_prev, L.anyc_partial_rows(B * h * w_), B * h * w_, gi_prev)
+        elif ctx.blur[k] is not None:
             # BlurPool block: through the stride-1 conv to the blurred tensor (its "BatchNorm" is the identity: ga = 1, gb = gmean = 0;
             # the mask [t > 0] only drops gradient that the producer's own mask drops as well - t = 0 means every tap was 0), then
             # through the fixed blur kernel (no weight gradient) to the block input
@@ -471,8 +563,10 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
                 main.wait_event(done)
             announce(pi, pi + 6)
     st0 = ctx.stages[0]
-    _, _, H, W = ctx.x.shape
-    L.call("ttk_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 1, p(wg_scratch), B, H, W, bf)
+    if c0 == _STEM_CHANNELS:
+        L.call("ttk_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 1, p(wg_scratch), B, H, W, bf)
+    else:
+        L.call("ttk_anyc_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 0, p(any_scratch), B, H, W, c0)
     if grad_ready_hook is not None:
         announce(0, 3)
     if side is not None:
@@ -485,11 +579,11 @@ class _MobileNetFn(torch.autograd.Function):
     """One autograd node for the whole backbone: saves raw conv outputs + BN constants."""
 
     @staticmethod
-    def forward(ctx, x, momentum, eps, buffers, frozen, blur, precision, *params):
+    def forward(ctx, x, momentum, eps, buffers, frozen, blur, precision, blocks, *params):
         if precision == "bf16-compute":
             feat, c = _mobilenet_bc.forward_impl(_THIS, x, params, buffers, momentum, eps, training=not frozen, frozen=frozen, blur=blur)
         else:
-            feat, c = _forward_impl(x, params, buffers, momentum, eps, training=not frozen, frozen=frozen, blur=blur)
+            feat, c = _forward_impl(x, params, buffers, momentum, eps, training=not frozen, frozen=frozen, blur=blur, blocks=blocks)
         ctx.c = c
         ctx.nparams = len(params)
         ctx.save_for_backward(*params)
@@ -503,7 +597,7 @@ class _MobileNetFn(torch.autograd.Function):
         else:
             grads = _backward_impl(ctx.c, gfeat.contiguous(), params)
         ctx.c = None
-        return (None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, *grads)
 
 
 class MobileNet(nn.Module):
@@ -512,8 +606,10 @@ class MobileNet(nn.Module):
     def __init__(self, num_classes=1000, widen_factor=1.0, input_channel=1, momentum=0.1, dropout=0.0,
                  use_blurpool=False, return_only_featuremap=False):
         super().__init__()
-        if widen_factor != 1.0 or input_channel != 1:
-            raise NotImplementedError("the HIP backbone is built for widen_factor=1.0, input_channel=1 (the pose estimator's configuration, models.py:220)")
+        if input_channel != 1:
+            raise NotImplementedError("the HIP backbone is built for input_channel=1 (the pose estimator's configuration, models.py:220)")
+        self.widen_factor = widen_factor
+        c0, self._blocks = _scaled_blocks(widen_factor)  # ValueError for a width the kernels do not take
         if return_only_featuremap:
             raise NotImplementedError("return_only_featuremap is not used by the pose estimator")
 
@@ -522,17 +618,17 @@ class MobileNet(nn.Module):
 
         self.use_blurpool = bool(use_blurpool)
         self.precision = None  # None = the module-wide default (set_activation_dtype); "fp32" | "bf16-compute" through set_precision
-        self.conv1 = nn.Conv2d(input_channel, 32, kernel_size=5, stride=2, padding=2, bias=False)
-        self.bn1 = NormalizationLayer(32, momentum=momentum)
+        self.conv1 = nn.Conv2d(input_channel, c0, kernel_size=5, stride=2, padding=2, bias=False)
+        self.bn1 = NormalizationLayer(c0, momentum=momentum)
         self.relu = ActivationFunc(inplace=True)
-        for name, cin, cout, stride in _BLOCKS:
+        for name, cin, cout, stride in self._blocks:
             setattr(self, name, block(cin, cout, stride))
         self.avgpool = nn.AdaptiveAvgPool2d(1)
-        self.num_features = 1024
-        self.num_intermediate_features = [64, 128, 256, 512, 1024]
+        self.num_features = int(1024 * widen_factor)  # reference :146,150
+        self.num_intermediate_features = [cout for name, _, cout, _ in self._blocks if name in _INTERMEDIATES]
         if num_classes:
             self.drop = nn.Dropout(p=dropout) if dropout > 0.0 else nn.Identity()
-            self.fc = nn.Linear(1024, num_classes)
+            self.fc = nn.Linear(self.num_features, num_classes)
         # reference :155-158 - N(0, sqrt(2/(k*k*Cout))) for EVERY conv, 1x1 included
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
@@ -542,23 +638,42 @@ class MobileNet(nn.Module):
     # ---- precision of the training kernels (an attribute of the instance; not in the checkpoint) ------------------
     def set_precision(self, mode):
         """"fp32" | "bf16-compute" for THIS backbone (None: follow the module-wide default again).  Returns self."""
-        self.precision = None if mode is None else _check_precision(mode)
+        mode = None if mode is None else _check_precision(mode)
+        self._check_width_precision(mode)
+        self.precision = mode
         return self
 
     def effective_precision(self) -> str:
         return self.precision if getattr(self, "precision", None) is not None else _DEFAULT_PRECISION
 
+    def _check_width_precision(self, mode):
+        if mode == "bf16-compute" and self._blocks != _BLOCKS:
+            raise ValueError(f'precision "bf16-compute" is built for widen_factor=1.0 only (its kernels work on 64-channel blocks); this backbone '
+                             f'has widen_factor={self.widen_factor}: use "fp32"')
+
+    def kernel_plan(self):
+        """[(layer, "tuned" | "anyc"), ...] in launch order: which kernel family runs each layer of the fp32 HIP path.  A shape the tuned
+        kernels accept (channel counts that are powers of two in 32..1024) runs on them; every other layer runs on the any-channel-count
+        family (ttk_anyc_*).  Pure Python; needs no GPU."""
+        fam = lambda ok: "tuned" if ok else "anyc"
+        plan = [("conv1", fam(self.conv1.out_channels == _STEM_CHANNELS))]
+        for name, cin, cout, _ in self._blocks:
+            plan.append((f"{name}.conv_dw", fam(_tuned_c(cin))))
+            plan.append((f"{name}.conv_sep", fam(_tuned_c(cin) and _tuned_c(cout))))
+        plan.append(("avgpool", fam(_tuned_c(self.num_features))))
+        return plan
+
     # ---- parameter plumbing -----------------------------------------------------------------
     def _bns(self):
         yield self.bn1
-        for name, *_ in _BLOCKS:
+        for name, *_ in self._blocks:
             blk = getattr(self, name)
             yield blk.bn_dw
             yield blk.bn_sep
 
     def _flat_params(self):
         ps = [self.conv1.weight, self.bn1.weight, self.bn1.bias]
-        for name, *_ in _BLOCKS:
+        for name, *_ in self._blocks:
             b = getattr(self, name)
             ps += [b.dw_weight, b.bn_dw.weight, b.bn_dw.bias, b.conv_sep.weight, b.bn_sep.weight, b.bn_sep.bias]
         return ps
@@ -567,7 +682,7 @@ class MobileNet(nn.Module):
         """Per block: the BlurPool2D kernel as a depthwise weight (use_blurpool, strided blocks) or None."""
         if not self.use_blurpool:
             return None
-        return [getattr(self, name).conv_dw[0].depthwise_weight() if getattr(self, name).blurpool else None for name, *_ in _BLOCKS]
+        return [getattr(self, name).conv_dw[0].depthwise_weight() if getattr(self, name).blurpool else None for name, *_ in self._blocks]
 
     def _flat_buffers(self):
         out = []
@@ -589,10 +704,11 @@ class MobileNet(nn.Module):
         if not x.is_cuda:
             return self._forward_torch(x)[0]
         momentum, eps = self._check(x)
+        self._check_width_precision(self.effective_precision())
         x = x.contiguous()
         bn_training = [bn.training for bn in self._bns()]
         if self.training and all(bn_training):
-            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), False, self._blur_weights(), self.effective_precision(), *self._flat_params())
+            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), False, self._blur_weights(), self.effective_precision(), self._blocks, *self._flat_params())
         if any(bn_training):
             raise NotImplementedError("mixed train/eval BatchNorm layers are not supported by the fused backbone")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params()):
@@ -601,12 +717,13 @@ class MobileNet(nn.Module):
             if any(p.requires_grad for bn in self._bns() for p in bn.parameters()):
                 raise NotImplementedError("eval-mode BatchNorm layers with trainable weight / bias are not built: freeze them "
                                           "(modelcomponents.freeze_norm_stats) or put the layers in training mode")
-            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), True, self._blur_weights(), self.effective_precision(), *self._flat_params())
+            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), True, self._blur_weights(), self.effective_precision(), self._blocks, *self._flat_params())
         if self.effective_precision() == "bf16-compute":
             feat, _ = _mobilenet_bc.forward_impl(_THIS, x, [q.detach() for q in self._flat_params()], self._flat_buffers(), momentum, eps, False,
                                                  blur=self._blur_weights())
         else:
-            feat, _ = _forward_impl(x, [q.detach() for q in self._flat_params()], self._flat_buffers(), momentum, eps, False, blur=self._blur_weights())
+            feat, _ = _forward_impl(x, [q.detach() for q in self._flat_params()], self._flat_buffers(), momentum, eps, False, blur=self._blur_weights(),
+                                    blocks=self._blocks)
         return feat
 
     def forward(self, x):
@@ -624,14 +741,15 @@ class MobileNet(nn.Module):
         momentum, eps = self._check(x)
         bufs = [b.clone() for b in self._flat_buffers()]  # do not double-update running statistics
         training = self.training
-        _, c = _forward_impl(x.contiguous(), [q.detach() for q in self._flat_params()], bufs, momentum, eps, training, blur=self._blur_weights())
+        _, c = _forward_impl(x.contiguous(), [q.detach() for q in self._flat_params()], bufs, momentum, eps, training, blur=self._blur_weights(),
+                             blocks=self._blocks)
         L, p = _hip.lib(), _hip.ptr
         outs = []
-        for k, (name, *_r) in enumerate(_BLOCKS):
+        for k, (name, *_r) in enumerate(self._blocks):
             if name in _INTERMEDIATES:
                 st = c.stages[2 * k + 2]
                 a = torch.empty_like(st.y)
-                L.call("ttk_bn_act", p(st.y), p(st.bn), p(st.skip), p(a), a.numel() // a.shape[-1], a.shape[-1])
+                L.call("ttk_bn_act" if _tuned_c(a.shape[-1]) else "ttk_anyc_bn_act", p(st.y), p(st.bn), p(st.skip), p(a), a.numel() // a.shape[-1], a.shape[-1])
                 outs.append(a.permute(0, 3, 1, 2))  # NCHW view of the channels-last copy ttk_bn_act wrote
         return outs
 
@@ -642,7 +760,7 @@ class MobileNet(nn.Module):
             raise RuntimeError("the MI355X training path needs CUDA tensors; CPU tensors are accepted in eval() mode only")
         x = self.relu(self.bn1(self.conv1(x)))
         outs = []
-        for name, *_ in _BLOCKS:
+        for name, *_ in self._blocks:
             x = getattr(self, name)(x)
             if name in _INTERMEDIATES:
                 outs.append(x)
