@@ -73,7 +73,11 @@ enum {
  * several workgroups raise with an integer atomicMax on the bit pattern, so the row must be ZERO before the forward
  * pass of a step (the shipped host allocates all blocks of a step from one zeroed arena).  0 = unknown: scale 1.
  *   ACT_BOUND >= max |max(scale*(y-mean)+beta, 0)|        written by ttk_bn_fwd_finalize (Cauchy-Schwarz on the batch
- *                                                         variance: |y-mean| <= sqrt(count*var)); eval: stays 0
+ *                                                         variance: |y-mean| <= sqrt(count*var)).  Eval-mode statistics:
+ *                                                         ttk_bn_eval_prepare leaves it alone (0 = unscaled) and
+ *                                                         ttk_bn_frozen_bound, which the host calls after it, raises it
+ *                                                         from this batch's partial sums:
+ *                                                         |scale|*(sqrt(count*var_b) + |mean_b-mean_run|) + |beta|
  *   GMAX      =  max |g|  of the gradient w.r.t. this layer's output, raised by the kernel that produces g
  *                                                         (ttk_avgpool_bwd, ttk_dwconv3x3_bwd_data)
  *   DY_BOUND  >= max |ga*(g-gmean) + gb*(y-mean)|         written by ttk_bn_bwd_finalize from GMAX and the variance */
