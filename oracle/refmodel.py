@@ -571,15 +571,15 @@ def loss_nllpoints3d(p, s, dim=3):  # negloglikelihood.py:145-166
 
 
 # ---- the non-default kinds of the loss switches (unused by the training script; pinned by tests/golden/loss_kinds.npz) ----------------
-def elem_distance(kind: str, p: Tensor, t: Tensor) -> Tensor:
-    """LOSS_OBJECT_MAP, losses.py:16-21: MSELoss / L1Loss / SmoothL1Loss(beta=0.01), reduction="none"."""
+def elem_distance(kind: str, p: Tensor, t: Tensor, beta: float = 0.01) -> Tensor:
+    """LOSS_OBJECT_MAP, losses.py:16-21: MSELoss / L1Loss / SmoothL1Loss(beta=0.01), reduction="none".  `beta` other than the
+    reference's 0.01: the per-row kernel tests, which put rows on either side of the kink."""
     e = p - t
     if kind == "l2":
         return e.square()
     if kind == "l1":
         return e.abs()
     assert kind == "smooth_l1"
-    beta = 0.01
     return torch.where(e.abs() < beta, 0.5 * e.square() / beta, e.abs() - 0.5 * beta)
 
 
