@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 29
+#define TTK_ABI_VERSION 30
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -635,6 +635,20 @@ int ttk_clip_adam(const int64_t* ptrs, const int32_t* numel, const int32_t* grou
  *   ttk_roi_transform  tr[B][2][3] = center_rotation(angle) @ range_remap(view_roi -> [0,N]^2) (:159-177)
  *   ttk_affine_warp    out[B][1][N][N] = bilinear(src[B][1][Hs][Ws], tr^-1(pixel centre)) * mul + add,
  *                      zero padding, align_corners=False; src uint8 (src_is_u8) or float32
+ *   ttk_area_crop      (ABI 30) same contract and arguments as ttk_affine_warp; the area-filtered (anti-aliased) crop
+ *                      of the reference's croprescale_image_cv2 / affine_transform_image_cv2 with downfilter="area"
+ *                      (tensors/image_geometric_cv2.py:65-155).  Per sample, with tr = rows (a, b, tx), (c, d, ty):
+ *                        Rx = max(N, rint(N / sqrt(a^2 + b^2))), Ry = max(N, rint(N / sqrt(c^2 + d^2)))
+ *                        I[p][q] = bilinear(src, tr^-1((q + .5) N / Rx, (p + .5) N / Ry) - .5), p < Ry, q < Rx, zero padding
+ *                        out[i][j] = mul * sum_p sum_q wy[i][p] wx[j][q] I[p][q] + add,
+ *                        wx[j][q] = |[q, q + 1) n [j Rx / N, (j + 1) Rx / N)| N / Rx (wy likewise; every row sums to 1)
+ *                      Axis-aligned tr (any mirror / quarter turn): the exact area average of the zero-padded integer
+ *                      view ROI = INTER_AREA without cv2's rounding to uint8 and without its dropping of coverages below
+ *                      1e-3.  Rx = Ry = N (magnification): ttk_affine_warp's crop.  Rotation: the reference's two stages
+ *                      (bilinear warp to source resolution, then area resize) with consistent pixel-centre geometry; cv2's
+ *                      warpAffine adds a 1/32-pixel coefficient grid and a half-pixel offset there, which is the one
+ *                      deviation.  The ratio Rx / N differs per sample and is unbounded (Rx, Ry are capped at 2^20 so
+ *                      that a degenerate tr terminates); no atomics, bitwise reproducible.
  *   ttk_affine_labels  in place: coord[B][3], pose[B][4] (ijkw), roi[B][4] (nullable each), pts_in ->
  *                      pts_out [B][68][3] (68-point flip map when det < 0); with N > 0 followed by the
  *                      pixel -> [-1,1] normalisation of normalize_batch (batch/normalization.py:20-56)
@@ -644,6 +658,8 @@ int ttk_view_roi(const float* face_roi, const float* scales, const float* transl
 int ttk_roi_transform(const int* view_roi, const float* angles, int B, int N, float* tr, ttk_stream_t stream);
 int ttk_affine_warp(const void* src, int src_is_u8, int B, int Hs, int Ws, const float* tr, float* out,
                     int N, float mul, float add, ttk_stream_t stream);
+int ttk_area_crop(const void* src, int src_is_u8, int B, int Hs, int Ws, const float* tr, float* out,
+                  int N, float mul, float add, ttk_stream_t stream);
 int ttk_affine_labels(const float* tr, int B, int N, float* coord, float* pose, float* roi,
                       const float* pts_in, float* pts_out, ttk_stream_t stream);
 

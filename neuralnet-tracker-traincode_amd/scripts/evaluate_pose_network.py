@@ -128,7 +128,7 @@ def evaluate(net_filename, data_name, roi_config: RoiConfig, args) -> dict:
     else:
         samples = pipelines.make_validation_loader(data_name, use_head_roi=roi_config.use_head_roi, return_single_samples=True, datadir=args.datadir)
     net = load_pose_network(net_filename, args.device)
-    predictor = E.Predictor(net, roi_config.expansion_factor, device=args.device)
+    predictor = E.Predictor(net, roi_config.expansion_factor, device=args.device, resample=getattr(args, "resample", "bilinear"))
     metrics = {"pose_errs": E.NormalizedXYSError()}
     if args.alignment_scheme == "none":
         metrics.update(geodesic_errs=E.GeodesicError(), euler_errs=E.EulerAngleErrors())
@@ -214,6 +214,8 @@ def make_parser():
     ap.add_argument("--allow-landmark-roi-fallback", action="store_true", default=False,
                     help="without the BFM head-mesh blob: evaluate the (H_roi) configurations with the landmark extent (F_roi) instead of failing")
     ap.add_argument("--ds", type=str, default="aflw2k3d", help="validation sets joined by '+', or paths of .npz files")
+    ap.add_argument("--resample", default="bilinear", choices=["bilinear", "area"],
+                    help="the crop's resampler: bilinear | area (the reference's anti-aliased crop; evaluate a network as it was trained)")
     ap.add_argument("--datadir", type=str, default=None, help="directory of the converted shards (default $DATADIR)")
     return ap
 

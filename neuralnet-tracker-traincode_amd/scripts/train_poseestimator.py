@@ -139,7 +139,7 @@ def setup_datasets(args, device, rank=0):
     """(train_loader, test_loader, size) - reference :66-78.  "synthetic": seeded synthetic crops; otherwise dataset ids read from the
     converted shards under $DATADIR (trackertraincode.pipelines.make_pose_estimation_loaders)."""
     common = dict(inputsize=args.input_size, batchsize=args.batchsize, device=device, seed=1234 + rank, enable_image_aug=args.with_image_aug,
-                  rotation_aug_angle=args.rotation_aug_angle, roi_override=args.roi_override)
+                  rotation_aug_angle=args.rotation_aug_angle, roi_override=args.roi_override, resample=getattr(args, "resample", "bilinear"))
     if args.ds == "synthetic":
         return trackertraincode.pipelines.make_pose_estimation_loaders(datasets="synthetic", **common)
     ids, weights = parse_dataset_definition(args.ds)
@@ -174,6 +174,9 @@ def make_parser():
     p.add_argument("--widen-factor", default=1.0, type=float, dest="widen_factor",
                    help="mobilenetv1: width multiplier of the backbone (the reference's MobileNet(widen_factor=...)): every channel count becomes "
                    "int(c * factor) and must be a multiple of 8 in 8..2048 - 0.25, 0.5, 0.75, 1.0, 1.5, 2.0; fp32 precision only")
+    p.add_argument("--resample", default="bilinear", choices=["bilinear", "area"],
+                   help="the crop's resampler in the train and the test loader: bilinear (four taps at the pixel centre) | area (the reference's "
+                   "anti-aliased INTER_AREA crop: trackertraincode.datatransformation.gpu.GpuFocusRoiAugment)")
     p.add_argument("--graph-steps", default=False, action="store_true",
                    help="single GPU: replay one captured hipGraph per training step instead of ~150 eager launches (train.GraphedTrainStep)")
     return p

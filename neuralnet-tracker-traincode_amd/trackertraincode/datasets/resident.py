@@ -258,13 +258,13 @@ class ResidentEvalLoader:
     pipelines.py:330-339 stage "eval"), label bookkeeping and whitening on the GPU."""
 
     def __init__(self, datasets: Sequence[ResidentFrames], batchsize: int, new_size: int = 129, extension_factor: float = 1.1,
-                 roi_from_landmarks: bool = False, device=None):
+                 roi_from_landmarks: bool = False, device=None, resample: str = "bilinear"):
         from ..datatransformation.batch.geometric import NoRoiRandomization
 
         self.datasets, self.batchsize = list(datasets), int(batchsize)
         self._device = _device_of(datasets, device)
         self._crop = GpuFocusRoiAugment(new_size=new_size, make_params=NoRoiRandomization(extension_factor), whiten=True,
-                                        roi_from_landmarks=roi_from_landmarks)
+                                        roi_from_landmarks=roi_from_landmarks, resample=resample)
 
     def __len__(self):
         return sum((len(d) + self.batchsize - 1) // self.batchsize for d in self.datasets)

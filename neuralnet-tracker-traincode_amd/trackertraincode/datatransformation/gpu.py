@@ -13,6 +13,14 @@ from .batch.geometric import MakeRoiRandomizationParameters, RoiFocusRandomizati
 
 _p = _hip.ptr
 
+RESAMPLE_MODES = ("bilinear", "area")
+
+
+def check_resample(resample) -> str:
+    if resample not in RESAMPLE_MODES:
+        raise ValueError(f"resample: got {resample!r}, expected one of {RESAMPLE_MODES}")
+    return resample
+
 
 class GpuFocusRoiAugment:
     """batch fields used: image u8/f32 [B,1,Hs,Ws] (grey levels 0..255), roi [B,4] (pixels), and - if present -
@@ -20,8 +28,14 @@ class GpuFocusRoiAugment:
     and labels in the crop's [-1,1] coordinates; other fields pass through."""
 
     def __init__(self, new_size=129, rotation_aug_angle=30.0, extension_factor=1.1, beyond_border_shift=0.3, whiten=True,
-                 make_params=None, flip_rot_p: float | None = None, roi_from_landmarks: bool = False):
-        """flip_rot_p: the reference's `horizontal_flip_and_rot_90(p_rot)` behind the crop (pipelines.py:373-377, batch/geometric.py:234-267):
+                 make_params=None, flip_rot_p: float | None = None, roi_from_landmarks: bool = False, resample: str = "bilinear"):
+        """resample: how the warp samples the source.  "bilinear" (default): four taps at the back-projected pixel centre whatever the
+        minification (ttk_affine_warp).  "area": the reference's resampler for crops that shrink their view ROI (croprescale_image_cv2 /
+        affine_transform_image_cv2 with downfilter="area", tensors/image_geometric_cv2.py:65-155) - the exact area average of the
+        zero-padded view ROI, a rotated crop through a bilinear source-resolution intermediate (ttk_area_crop; include/ttk.h has the
+        definition and its one deviation from cv2); a crop that magnifies is the bilinear one.  Only the warp launch differs: view_roi,
+        transform, labels and whitening are those of "bilinear".  `params.downfilter` is NOT read.
+        flip_rot_p: the reference's `horizontal_flip_and_rot_90(p_rot)` behind the crop (pipelines.py:373-377, batch/geometric.py:234-267):
         every sample is mirrored with probability 1/2 and turned by +-90 degrees with probability p_rot / 2 each; None = off (the eval
         stage).  roi_from_landmarks: `roi_override="landmarks"` (pipelines.py:343-350, batch/misc.py:9-31): the face box the crop is taken
         around AND the box label of the crop are the xy extent of pt3d_68 (samples without landmarks keep their stored box)."""
@@ -31,6 +45,7 @@ class GpuFocusRoiAugment:
         self.mul, self.add = 1.0 / 256.0, (-0.5 if whiten else 0.0)
         self.flip_rot_p = None if flip_rot_p is None else float(flip_rot_p)
         self.roi_from_landmarks = bool(roi_from_landmarks)
+        self.resample = check_resample(resample)
         self._fliprot = None  # [6, 3, 3]: the six point transforms (rot_dir + 1) * 2 + do_flip in crop pixels, built on first use
 
     def fliprot_table(self) -> torch.Tensor:
@@ -98,7 +113,7 @@ class GpuFocusRoiAugment:
         src = img.contiguous()
         if src.dtype not in (torch.uint8, torch.float32):
             src = src.float()
-        L.call("ttk_affine_warp", _p(src), int(src.dtype == torch.uint8), B, Hs, Ws, _p(tr), _p(out_img), self.new_size, self.mul, self.add)
+        L.call("ttk_area_crop" if self.resample == "area" else "ttk_affine_warp", _p(src), int(src.dtype == torch.uint8), B, Hs, Ws, _p(tr), _p(out_img), self.new_size, self.mul, self.add)
         out = {k: v for k, v in batch.items()}
         out["image"] = out_img
         coord = f32(batch["coord"]).clone() if "coord" in batch else None

@@ -32,10 +32,12 @@ class Predictor:
     network outputs mapped back to image coordinates: coord [B,3] (x, y, head size in pixels), pose [B,4], roi [B,4],
     pt3d_68 [B,68,3] (when the network has the landmark head) - reference :185-208."""
 
-    def __init__(self, net: torch.nn.Module, focus_roi_expansion_factor: float = 1.1, device: str | torch.device = "cuda"):
+    def __init__(self, net: torch.nn.Module, focus_roi_expansion_factor: float = 1.1, device: str | torch.device = "cuda",
+                 resample: str = "bilinear"):
         self._net = net.to(device).eval()
         self._device = torch.device(device)
-        self._crop = GpuFocusRoiAugment(new_size=net.input_resolution, make_params=NoRoiRandomization(focus_roi_expansion_factor))
+        self._crop = GpuFocusRoiAugment(new_size=net.input_resolution, make_params=NoRoiRandomization(focus_roi_expansion_factor),
+                                        resample=resample)
 
     @property
     def input_resolution(self) -> int:

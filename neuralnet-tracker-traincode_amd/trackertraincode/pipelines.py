@@ -248,7 +248,8 @@ def _slice_frames(frames, lo, hi):
 
 def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights=None, use_weights_as_sampling_frequency=True,
                                  enable_image_aug=True, rotation_aug_angle=30.0, roi_override="original", device="cuda", seed=1234,
-                                 datadir=None, steps_per_epoch=None, headmodel=None, frames_on="auto", hbm_budget_bytes=None):
+                                 datadir=None, steps_per_epoch=None, headmodel=None, frames_on="auto", hbm_budget_bytes=None,
+                                 resample="bilinear"):
     """Signature of the reference (pipelines.py:359-369) plus `seed` (data-parallel replicas draw different streams), `datadir` and
     `steps_per_epoch`.  `datasets`:
 
@@ -267,7 +268,12 @@ def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights
         `frames_on`: "device" (decoded frames live in HBM), "host" (pinned host memory, gathered and copied per step on a side stream, one
         step ahead: datasets/resident.py) or "auto": in HBM while the decoded shards stay within `hbm_budget_bytes` (default: half of
         the device's memory), the largest datasets on the host beyond that.
+        `resample`: "bilinear" (default) or "area", the crop's resampler in the train AND the test loader (GpuFocusRoiAugment; the
+        synthetic loaders draw finished crops and have none).
     """
+    from .datatransformation.gpu import check_resample
+
+    check_resample(resample)
     if datasets == "synthetic":
         datasets = [(Tag.POSE_WITH_LANDMARKS, 11.0), (Tag.POSE_WITH_LMKS_NO_SHAPE_PARAMS, 1.0)]
     if isinstance(datasets, (list, tuple)) and datasets and isinstance(datasets[0], tuple) and isinstance(datasets[0][0], Tag):
@@ -352,10 +358,10 @@ def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights
         freqs = [1.0 / len(weights)] * len(weights)
     augs = make_image_augmentations(torch.Generator().manual_seed(99 + seed)) if enable_image_aug else None
     crop = GpuFocusRoiAugment(new_size=inputsize, rotation_aug_angle=rotation_aug_angle, extension_factor=extension_factor, whiten=not augs,
-                              flip_rot_p=0.01, roi_from_landmarks=roi_override == "landmarks")
+                              flip_rot_p=0.01, roi_from_landmarks=roi_override == "landmarks", resample=resample)
     steps = steps_per_epoch if steps_per_epoch is not None else (10 * 1024) // batchsize  # Trainer(limit_train_batches=...), train_poseestimator.py:447
     train = ResidentLoader(train_sets, freqs, batchsize, steps, seed=seed, crop=crop, image_augmentations=augs, device=device)
     tname, ttag, (lo, hi) = _TEST_SHARD
     test = ResidentEvalLoader([_slice_frames(shard(tname, ttag), lo, hi)], batchsize * 2, new_size=inputsize, extension_factor=extension_factor,
-                              roi_from_landmarks=roi_override == "landmarks", device=device)
+                              roi_from_landmarks=roi_override == "landmarks", device=device, resample=resample)
     return train, test, total
