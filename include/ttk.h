@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 30
+#define TTK_ABI_VERSION 31
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -579,6 +579,23 @@ typedef struct ttk_loss_op {
   double d;
 } ttk_loss_op;
 int ttk_loss_batch(int nops, const ttk_loss_op* ops, ttk_stream_t stream);
+
+/* ttk_loss_batch with ROW LIVENESS: one launch whose ops cover only the rows of certain dataset Tags, so that a training step over
+ * sub-batches of several Tags can be written over all B rows with launch arguments that do not depend on the split (reference
+ * train.py:372-439: a sub-batch of Tag T contributes the terms of T's criterion table; here row i contributes the terms whose Tag set
+ * holds tag_code[i]).  tag_code[] (DEVICE, one int per row, valid codes 0..31 - the reference's Tag values are below 32) is shared by
+ * all ops of the launch and must cover the largest row count among them; tag_sets[] (HOST, nops entries, parallel to ops[] - ttk_loss_op
+ * itself is unchanged, so ttk_loss_batch callers stay valid) holds per op the 32-bit set of codes it covers.  Row i of op k is live iff
+ * 0 <= tag_code[i] < 32 and bit tag_code[i] of tag_sets[k] is set.  A dead row does no arithmetic and reads none of its inputs (its
+ * target row may hold NaN or stale labels): forward ops write the value 0.0f (gmm: and zero responsibilities), backward ops write 0.0f
+ * to that row of every gradient output.  No atomics, no host reads.  tag_code == NULL: every row is live, the call IS ttk_loss_batch.
+ *
+ * ttk_row_weights: rw[k][i] = wtable[k * 32 + tag_code[i]] * (dataset_weight ? dataset_weight[i] : 1) for K terms and n rows in one
+ * launch (codes outside 0..31: 0).  wtable[K][32] is DEVICE memory: term k's weight for every Tag code (0 where the Tag lacks the
+ * term), rewritten by the host when the epoch's weights change - outside a captured graph, like the TTK_ADAM_HYPER block.  The loss
+ * sum of the flat step is ttk_weighted_sum_fwd / _bwd with w[k] = 1, sample_w[k] = rw[k], count[k] = n, scale = 1 / n. */
+int ttk_loss_batch_rows(int nops, const ttk_loss_op* ops, const unsigned* tag_sets, const int* tag_code, ttk_stream_t stream);
+int ttk_row_weights(const float* wtable, const int* tag_code, const float* dataset_weight, int K, int n, float* rw, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-GPU intensity augmentation - the kornia chain of trackertraincode/pipelines.py:508-532

@@ -35,28 +35,71 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;              \
   if (s >= (n)) return;
 
-__device__ __forceinline__ void loss_rot_fwd_body(const float* q, const float* t, int n, float* v) {
+// Row liveness (ttk_loss_batch_rows): row s of an op is live iff bit tag[s] of the op's Tag set is set.  A dead row does no arithmetic and
+// reads none of its inputs (its target may hold NaN): the value and the row of every gradient output become 0.  Every body takes a Live
+// as its last argument; the default - no tag array, what the single-op kernels and ttk_loss_batch pass - is a compile-time constant
+// after inlining, so those kernels carry no check.  The wave-per-sample bodies decide before their first shuffle; s is the same in all
+// lanes of a wave there, so the exit is wave-uniform.
+struct Live {
+  const int* tag = nullptr;
+  unsigned set = 0u;
+  __device__ __forceinline__ bool operator()(int s) const {
+    if (!tag) return true;
+    const unsigned c = (unsigned)tag[s];
+    return c < 32u && ((set >> c) & 1u) != 0u;
+  }
+};
+__device__ __forceinline__ void zero_row(float* g, int s, int w) {
+  for (int j = 0; j < w; ++j) g[(size_t)s * w + j] = 0.f;
+}
+#define TTK_DEAD_VALUE(v)  \
+  if (!live(s)) {          \
+    v[s] = 0.f;            \
+    return;                \
+  }
+#define TTK_DEAD_WAVE_VALUE(v)   \
+  if (!live(s)) {                \
+    if (lane == 0) v[s] = 0.f;   \
+    return;                      \
+  }
+
+__device__ __forceinline__ void loss_rot_fwd_body(const float* q, const float* t, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::rot_loss(q + 4 * s, t + 4 * s);
 }
-__device__ __forceinline__ void loss_rot_bwd_body(const float* q, const float* t, const float* gv, int n, float* gq) {
+__device__ __forceinline__ void loss_rot_bwd_body(const float* q, const float* t, const float* gv, int n, float* gq, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gq, s, 4);
+    return;
+  }
   lm::rot_loss_bwd(q + 4 * s, t + 4 * s, gv[s], gq + 4 * s);
 }
-__device__ __forceinline__ void loss_rot6d_fwd_body(const float* R, const float* t, int n, float* v) {
+__device__ __forceinline__ void loss_rot6d_fwd_body(const float* R, const float* t, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::rot6d_loss(R + 9 * s, t + 4 * s);
 }
-__device__ __forceinline__ void loss_rot6d_bwd_body(const float* t, const float* gv, int n, float* gR) {
+__device__ __forceinline__ void loss_rot6d_bwd_body(const float* t, const float* gv, int n, float* gR, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gR, s, 9);
+    return;
+  }
   lm::rot6d_loss_bwd(t + 4 * s, gv[s], gR + 9 * s);
 }
-__device__ __forceinline__ void loss_ortho6d_fwd_body(const float* z, int n, float* v) {
+__device__ __forceinline__ void loss_ortho6d_fwd_body(const float* z, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::ortho6d_loss(z + 6 * s);
 }
-__device__ __forceinline__ void loss_ortho6d_bwd_body(const float* z, const float* gv, int n, float* gz) {
+__device__ __forceinline__ void loss_ortho6d_bwd_body(const float* z, const float* gv, int n, float* gz, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gz, s, 6);
+    return;
+  }
   lm::ortho6d_loss_bwd(z + 6 * s, gv[s], gz + 6 * s);
 }
 __global__ void mat_to_quat_fwd_k(const float* m, int n, float* q) {
@@ -67,17 +110,23 @@ __global__ void mat_to_quat_bwd_k(const float* m, const float* gq, int n, float*
   TTK_SAMPLE_INDEX(n);
   lm::from_matrix_bwd(m + 9 * s, gq + 4 * s, gm + 9 * s);
 }
-__device__ __forceinline__ void loss_quatreg_fwd_body(const float* q, int n, float* v) {
+__device__ __forceinline__ void loss_quatreg_fwd_body(const float* q, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::quatreg_loss(q + 4 * s);
 }
-__device__ __forceinline__ void loss_quatreg_bwd_body(const float* q, const float* gv, int n, float* gq) {
+__device__ __forceinline__ void loss_quatreg_bwd_body(const float* q, const float* gv, int n, float* gq, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gq, s, 4);
+    return;
+  }
   lm::quatreg_loss_bwd(q + 4 * s, gv[s], gq + 4 * s);
 }
 // mean_d (p - t)^2
-__device__ __forceinline__ void loss_mse_rows_fwd_body(const float* p, const float* t, int n, int D, float* v) {
+__device__ __forceinline__ void loss_mse_rows_fwd_body(const float* p, const float* t, int n, int D, float* v, const Live live = {}) {
   TTK_WAVE_SAMPLE(n);
+  TTK_DEAD_WAVE_VALUE(v);
   float acc = 0.f;
   for (int d = lane; d < D; d += 64) {
     const float e = p[(size_t)s * D + d] - t[(size_t)s * D + d];
@@ -86,15 +135,20 @@ __device__ __forceinline__ void loss_mse_rows_fwd_body(const float* p, const flo
   acc = wave_sum_f(acc);
   if (lane == 0) v[s] = acc / (float)D;
 }
-__device__ __forceinline__ void loss_mse_rows_bwd_body(const float* p, const float* t, const float* gv, int n, int D, float* gp) {
+__device__ __forceinline__ void loss_mse_rows_bwd_body(const float* p, const float* t, const float* gv, int n, int D, float* gp, const Live live = {}) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * D) return;
+  if (!live(i / D)) {
+    gp[i] = 0.f;
+    return;
+  }
   gp[i] = 2.f * (p[i] - t[i]) * gv[i / D] / (float)D;
 }
 // the same over the column window [c0, c0 + Dc) of rows that are Dt floats apart (p and t alike); the gradient is written
 // for the whole row, zero outside the window
-__device__ __forceinline__ void loss_mse_cols_fwd_body(const float* p, const float* t, int n, int Dt, int c0, int Dc, float* v) {
+__device__ __forceinline__ void loss_mse_cols_fwd_body(const float* p, const float* t, int n, int Dt, int c0, int Dc, float* v, const Live live = {}) {
   TTK_WAVE_SAMPLE(n);
+  TTK_DEAD_WAVE_VALUE(v);
   float acc = 0.f;
   for (int d = lane; d < Dc; d += 64) {
     const float e = p[(size_t)s * Dt + c0 + d] - t[(size_t)s * Dt + c0 + d];
@@ -103,9 +157,13 @@ __device__ __forceinline__ void loss_mse_cols_fwd_body(const float* p, const flo
   acc = wave_sum_f(acc);
   if (lane == 0) v[s] = acc / (float)Dc;
 }
-__device__ __forceinline__ void loss_mse_cols_bwd_body(const float* p, const float* t, const float* gv, int n, int Dt, int c0, int Dc, float* gp) {
+__device__ __forceinline__ void loss_mse_cols_bwd_body(const float* p, const float* t, const float* gv, int n, int Dt, int c0, int Dc, float* gp, const Live live = {}) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * Dt) return;
+  if (!live(i / Dt)) {
+    gp[i] = 0.f;
+    return;
+  }
   const int d = i % Dt - c0;
   gp[i] = (d >= 0 && d < Dc) ? 2.f * (p[i] - t[i]) * gv[i / Dt] / (float)Dc : 0.f;
 }
@@ -113,8 +171,9 @@ __device__ __forceinline__ void loss_mse_cols_bwd_body(const float* p, const flo
 // The non-default kinds of the reference's loss switches (losses.py:16-38): v[s] = sum_d colw[d] * f_kind(p[s][d] - t[s][d]) over rows of
 // D floats.  The host folds the reduction of each loss class into colw (mean over a column window: 1/Dc inside, 0 outside; landmarks:
 // point weight / 68 on the first `dim` coordinates of each point).
-__device__ __forceinline__ void loss_elem_fwd_body(const float* p, const float* t, const float* colw, int n, int D, int kind, float beta, float* v) {
+__device__ __forceinline__ void loss_elem_fwd_body(const float* p, const float* t, const float* colw, int n, int D, int kind, float beta, float* v, const Live live = {}) {
   TTK_WAVE_SAMPLE(n);
+  TTK_DEAD_WAVE_VALUE(v);
   float acc = 0.f;
   for (int d = lane; d < D; d += 64) {
     const float w = colw[d];
@@ -124,18 +183,27 @@ __device__ __forceinline__ void loss_elem_fwd_body(const float* p, const float* 
   if (lane == 0) v[s] = acc;
 }
 __device__ __forceinline__ void loss_elem_bwd_body(const float* p, const float* t, const float* colw, const float* gv, int n, int D, int kind, float beta,
-                                                   float* gp) {
+                                                   float* gp, const Live live = {}) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * D) return;
+  if (!live(i / D)) {
+    gp[i] = 0.f;
+    return;
+  }
   const float w = colw[i % D];
   gp[i] = w != 0.f ? w * lm::elem_loss_d(kind, p[i] - t[i], beta) * gv[i / D] : 0.f;
 }
-__device__ __forceinline__ void loss_rot_geodesic_fwd_body(const float* q, const float* t, int n, float* v) {
+__device__ __forceinline__ void loss_rot_geodesic_fwd_body(const float* q, const float* t, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::smooth_geodesic_loss(q + 4 * s, t + 4 * s);
 }
-__device__ __forceinline__ void loss_rot_geodesic_bwd_body(const float* q, const float* t, const float* gv, int n, float* gq) {
+__device__ __forceinline__ void loss_rot_geodesic_bwd_body(const float* q, const float* t, const float* gv, int n, float* gq, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gq, s, 4);
+    return;
+  }
   lm::smooth_geodesic_loss_bwd(q + 4 * s, t + 4 * s, gv[s], gq + 4 * s);
 }
 
@@ -194,8 +262,9 @@ __global__ void weighted_sum_bwd_k(SumTerms a, float scale, const float* gout) {
   }
 }
 // mean_p( w_p * sum_{d<dim} (p - t)^2 )
-__device__ __forceinline__ void loss_points_fwd_body(const float* p, const float* t, int n, int dim, float chin, float eye, float* v) {
+__device__ __forceinline__ void loss_points_fwd_body(const float* p, const float* t, int n, int dim, float chin, float eye, float* v, const Live live = {}) {
   TTK_WAVE_SAMPLE(n);
+  TTK_DEAD_WAVE_VALUE(v);
   float acc = 0.f;
   for (int k = lane; k < 68; k += 64) {
     float e2 = 0.f;
@@ -209,34 +278,51 @@ __device__ __forceinline__ void loss_points_fwd_body(const float* p, const float
   if (lane == 0) v[s] = acc / 68.f;
 }
 __device__ __forceinline__ void loss_points_bwd_body(const float* p, const float* t, const float* gv, int n, int dim, float chin, float eye,
-                                  float* gp) {
+                                  float* gp, const Live live = {}) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * 204) return;
   const int s = i / 204, r = i % 204, k = r / 3, d = r % 3;
+  if (!live(s)) {
+    gp[i] = 0.f;
+    return;
+  }
   gp[i] = d < dim ? 2.f * lm::point_weight(k, chin, eye) * (p[i] - t[i]) * gv[s] / 68.f : 0.f;
 }
-__device__ __forceinline__ void loss_nllrot_fwd_body(const float* q, const float* t, const float* L, int n, float* v) {
+__device__ __forceinline__ void loss_nllrot_fwd_body(const float* q, const float* t, const float* L, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::nllrot_loss(q + 4 * s, t + 4 * s, L + 9 * s);
 }
-__device__ __forceinline__ void loss_nllrot_bwd_body(const float* q, const float* t, const float* L, const float* gv, int n, float* gq, float* gL) {
+__device__ __forceinline__ void loss_nllrot_bwd_body(const float* q, const float* t, const float* L, const float* gv, int n, float* gq, float* gL, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gq, s, 4);
+    zero_row(gL, s, 9);
+    return;
+  }
   lm::nllrot_loss_bwd(q + 4 * s, t + 4 * s, L + 9 * s, gv[s], gq + 4 * s, gL + 9 * s);
 }
-__device__ __forceinline__ void loss_nllcoord_fwd_body(const float* c, const float* t, const float* L, int n, float* v) {
+__device__ __forceinline__ void loss_nllcoord_fwd_body(const float* c, const float* t, const float* L, int n, float* v, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  TTK_DEAD_VALUE(v);
   v[s] = lm::nllcoord_loss(c + 3 * s, t + 3 * s, L + 9 * s);
 }
-__device__ __forceinline__ void loss_nllcoord_bwd_body(const float* c, const float* t, const float* L, const float* gv, int n, float* gc, float* gL) {
+__device__ __forceinline__ void loss_nllcoord_bwd_body(const float* c, const float* t, const float* L, const float* gv, int n, float* gc, float* gL, const Live live = {}) {
   TTK_SAMPLE_INDEX(n);
+  if (!live(s)) {
+    zero_row(gc, s, 3);
+    zero_row(gL, s, 9);
+    return;
+  }
   lm::nllcoord_loss_bwd(c + 3 * s, t + 3 * s, L + 9 * s, gv[s], gc + 3 * s, gL + 9 * s);
 }
 // -mean over `per` elements of w * Normal(mu, sigma).log_prob(x); elements laid out [n][rows][3] with
 // only the first `dim` of every 3 used when rows3 != 0 (points), else plain [n][per].
 template <bool LAPLACE = false>
 __device__ __forceinline__ void loss_normal_fwd_body(const float* mu, const float* sg, const float* x, int n, int per, int points, int dim,
-                                  float chin, float eye, float* v) {
+                                  float chin, float eye, float* v, const Live live = {}) {
   TTK_WAVE_SAMPLE(n);
+  TTK_DEAD_WAVE_VALUE(v);
   float acc = 0.f;
   if (points) {
     for (int k = lane; k < 68; k += 64) {
@@ -260,11 +346,16 @@ __device__ __forceinline__ void loss_normal_fwd_body(const float* mu, const floa
 }
 template <bool LAPLACE = false>
 __device__ __forceinline__ void loss_normal_bwd_body(const float* mu, const float* sg, const float* x, const float* gv, int n, int per,
-                                  int points, int dim, float chin, float eye, float* gmu, float* gsg) {
+                                  int points, int dim, float chin, float eye, float* gmu, float* gsg, const Live live = {}) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int stride = points ? 204 : per;
   if (i >= n * stride) return;
   const int s = i / stride, r = i % stride;
+  if (!live(s)) {
+    gmu[i] = 0.f;
+    gsg[i] = 0.f;
+    return;
+  }
   float w;
   if (points) {
     const int k = r / 3, d = r % 3;
@@ -281,8 +372,13 @@ __device__ __forceinline__ void loss_normal_bwd_body(const float* mu, const floa
   gsg[i] = b;
 }
 __device__ __forceinline__ void loss_gmm_fwd_body(const float* x, const double* ck, const double* mu, const double* sinv, int K, double fudge,
-                               int n, float* v, double* post) {
+                               int n, float* v, double* post, const Live live = {}) {
   TTK_WAVE_SAMPLE(n);
+  if (!live(s)) {  // (the responsibilities of a dead row are never read; they are written so that no output is left undefined)
+    if (lane < K) post[(size_t)K * s + lane] = 0.0;
+    if (lane == 0) v[s] = 0.f;
+    return;
+  }
   double a[16];
   const double xd = lane < 50 ? (double)x[50 * s + lane] : 0.0;
   double mx = -1.0e300;
@@ -303,10 +399,14 @@ __device__ __forceinline__ void loss_gmm_fwd_body(const float* x, const double* 
 }
 // d/dx_d = fudge * sum_k post_k (x_d - mu_kd) sinv_kd^2
 __device__ __forceinline__ void loss_gmm_bwd_body(const float* x, const double* mu, const double* sinv, const double* post, int K, double fudge,
-                               const float* gv, int n, float* gx) {
+                               const float* gv, int n, float* gx, const Live live = {}) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * 50) return;
   const int s = i / 50, d = i % 50;
+  if (!live(s)) {
+    gx[i] = 0.f;
+    return;
+  }
   double acc = 0.0;
   for (int k = 0; k < K; ++k) {
     const double si = sinv[k * 50 + d];
@@ -356,34 +456,50 @@ struct BatchArgs {
 #define P_(k) static_cast<const float*>(o.p[k])
 #define W_(k) static_cast<float*>(const_cast<void*>(o.p[k]))
 #define D_(k) static_cast<const double*>(o.p[k])
-__global__ void __launch_bounds__(256) loss_batch_k(BatchArgs a) {
-  const ttk_loss_op& o = a.op[blockIdx.y];
+__device__ __forceinline__ void loss_batch_dispatch(const ttk_loss_op& o, const Live live) {
   if ((long long)blockIdx.x * 256 >= (long long)o.items) return;
   switch (o.kind) {
-    case TTK_OP_ROT_FWD: loss_rot_fwd_body(P_(0), P_(1), o.i[0], W_(2)); break;
-    case TTK_OP_ROT_BWD: loss_rot_bwd_body(P_(0), P_(1), P_(2), o.i[0], W_(3)); break;
-    case TTK_OP_ROT6D_FWD: loss_rot6d_fwd_body(P_(0), P_(1), o.i[0], W_(2)); break;
-    case TTK_OP_ROT6D_BWD: loss_rot6d_bwd_body(P_(0), P_(1), o.i[0], W_(2)); break;
-    case TTK_OP_ORTHO6D_FWD: loss_ortho6d_fwd_body(P_(0), o.i[0], W_(1)); break;
-    case TTK_OP_ORTHO6D_BWD: loss_ortho6d_bwd_body(P_(0), P_(1), o.i[0], W_(2)); break;
-    case TTK_OP_QUATREG_FWD: loss_quatreg_fwd_body(P_(0), o.i[0], W_(1)); break;
-    case TTK_OP_QUATREG_BWD: loss_quatreg_bwd_body(P_(0), P_(1), o.i[0], W_(2)); break;
-    case TTK_OP_MSE_ROWS_FWD: loss_mse_rows_fwd_body(P_(0), P_(1), o.i[0], o.i[1], W_(2)); break;
-    case TTK_OP_MSE_ROWS_BWD: loss_mse_rows_bwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], W_(3)); break;
-    case TTK_OP_MSE_COLS_FWD: loss_mse_cols_fwd_body(P_(0), P_(1), o.i[0], o.i[1], o.i[2], o.i[3], W_(2)); break;
-    case TTK_OP_MSE_COLS_BWD: loss_mse_cols_bwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], o.i[2], o.i[3], W_(3)); break;
-    case TTK_OP_POINTS_FWD: loss_points_fwd_body(P_(0), P_(1), o.i[0], o.i[1], o.f[0], o.f[1], W_(2)); break;
-    case TTK_OP_POINTS_BWD: loss_points_bwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], o.f[0], o.f[1], W_(3)); break;
-    case TTK_OP_NLLROT_FWD: loss_nllrot_fwd_body(P_(0), P_(1), P_(2), o.i[0], W_(3)); break;
-    case TTK_OP_NLLROT_BWD: loss_nllrot_bwd_body(P_(0), P_(1), P_(2), P_(3), o.i[0], W_(4), W_(5)); break;
-    case TTK_OP_NLLCOORD_FWD: loss_nllcoord_fwd_body(P_(0), P_(1), P_(2), o.i[0], W_(3)); break;
-    case TTK_OP_NLLCOORD_BWD: loss_nllcoord_bwd_body(P_(0), P_(1), P_(2), P_(3), o.i[0], W_(4), W_(5)); break;
-    case TTK_OP_NORMAL_FWD: loss_normal_fwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.f[1], W_(3)); break;
-    case TTK_OP_NORMAL_BWD: loss_normal_bwd_body(P_(0), P_(1), P_(2), P_(3), o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.f[1], W_(4), W_(5)); break;
-    case TTK_OP_GMM_FWD: loss_gmm_fwd_body(P_(0), D_(1), D_(2), D_(3), o.i[0], o.d, o.i[1], W_(4), static_cast<double*>(const_cast<void*>(o.p[5]))); break;
-    case TTK_OP_GMM_BWD: loss_gmm_bwd_body(P_(0), D_(1), D_(2), D_(3), o.i[0], o.d, P_(4), o.i[1], W_(5)); break;
+    case TTK_OP_ROT_FWD: loss_rot_fwd_body(P_(0), P_(1), o.i[0], W_(2), live); break;
+    case TTK_OP_ROT_BWD: loss_rot_bwd_body(P_(0), P_(1), P_(2), o.i[0], W_(3), live); break;
+    case TTK_OP_ROT6D_FWD: loss_rot6d_fwd_body(P_(0), P_(1), o.i[0], W_(2), live); break;
+    case TTK_OP_ROT6D_BWD: loss_rot6d_bwd_body(P_(0), P_(1), o.i[0], W_(2), live); break;
+    case TTK_OP_ORTHO6D_FWD: loss_ortho6d_fwd_body(P_(0), o.i[0], W_(1), live); break;
+    case TTK_OP_ORTHO6D_BWD: loss_ortho6d_bwd_body(P_(0), P_(1), o.i[0], W_(2), live); break;
+    case TTK_OP_QUATREG_FWD: loss_quatreg_fwd_body(P_(0), o.i[0], W_(1), live); break;
+    case TTK_OP_QUATREG_BWD: loss_quatreg_bwd_body(P_(0), P_(1), o.i[0], W_(2), live); break;
+    case TTK_OP_MSE_ROWS_FWD: loss_mse_rows_fwd_body(P_(0), P_(1), o.i[0], o.i[1], W_(2), live); break;
+    case TTK_OP_MSE_ROWS_BWD: loss_mse_rows_bwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], W_(3), live); break;
+    case TTK_OP_MSE_COLS_FWD: loss_mse_cols_fwd_body(P_(0), P_(1), o.i[0], o.i[1], o.i[2], o.i[3], W_(2), live); break;
+    case TTK_OP_MSE_COLS_BWD: loss_mse_cols_bwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], o.i[2], o.i[3], W_(3), live); break;
+    case TTK_OP_POINTS_FWD: loss_points_fwd_body(P_(0), P_(1), o.i[0], o.i[1], o.f[0], o.f[1], W_(2), live); break;
+    case TTK_OP_POINTS_BWD: loss_points_bwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], o.f[0], o.f[1], W_(3), live); break;
+    case TTK_OP_NLLROT_FWD: loss_nllrot_fwd_body(P_(0), P_(1), P_(2), o.i[0], W_(3), live); break;
+    case TTK_OP_NLLROT_BWD: loss_nllrot_bwd_body(P_(0), P_(1), P_(2), P_(3), o.i[0], W_(4), W_(5), live); break;
+    case TTK_OP_NLLCOORD_FWD: loss_nllcoord_fwd_body(P_(0), P_(1), P_(2), o.i[0], W_(3), live); break;
+    case TTK_OP_NLLCOORD_BWD: loss_nllcoord_bwd_body(P_(0), P_(1), P_(2), P_(3), o.i[0], W_(4), W_(5), live); break;
+    case TTK_OP_NORMAL_FWD: loss_normal_fwd_body(P_(0), P_(1), P_(2), o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.f[1], W_(3), live); break;
+    case TTK_OP_NORMAL_BWD: loss_normal_bwd_body(P_(0), P_(1), P_(2), P_(3), o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.f[1], W_(4), W_(5), live); break;
+    case TTK_OP_GMM_FWD: loss_gmm_fwd_body(P_(0), D_(1), D_(2), D_(3), o.i[0], o.d, o.i[1], W_(4), static_cast<double*>(const_cast<void*>(o.p[5])), live); break;
+    case TTK_OP_GMM_BWD: loss_gmm_bwd_body(P_(0), D_(1), D_(2), D_(3), o.i[0], o.d, P_(4), o.i[1], W_(5), live); break;
     default: break;
   }
+}
+__global__ void __launch_bounds__(256) loss_batch_k(BatchArgs a) { loss_batch_dispatch(a.op[blockIdx.y], Live{}); }
+// ttk_loss_batch_rows: the same ops, each with the set of Tag codes whose rows it covers; tag[] holds one code per row
+struct TagSets {
+  unsigned set[kBatchMax];
+};
+__global__ void __launch_bounds__(256) loss_batch_rows_k(BatchArgs a, TagSets m, const int* tag) {
+  loss_batch_dispatch(a.op[blockIdx.y], Live{tag, m.set[blockIdx.y]});
+}
+// rw[k][i] = wtable[k][tag[i]] * dataset_weight[i]: the per-row weight of term k (0 where the row's Tag lacks the term)
+__global__ void row_weights_k(const float* wtable, const int* tag, const float* dw, int K, int n, float* rw) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= K * n) return;
+  const int k = i / n, r = i % n;
+  const unsigned c = (unsigned)tag[r];
+  const float w = c < 32u ? wtable[k * 32 + c] : 0.f;
+  rw[i] = w * (dw ? dw[r] : 1.f);
 }
 #undef P_
 #undef W_
@@ -631,6 +747,26 @@ int ttk_loss_batch(int nops, const ttk_loss_op* ops, ttk_stream_t stream) {
   }
   hipLaunchKernelGGL(loss_batch_k, dim3((unsigned)((items + 255) / 256), (unsigned)nops), dim3(256), 0, (hipStream_t)stream, a);
   TTK_LAUNCH_CHECK("loss_batch");
+}
+int ttk_loss_batch_rows(int nops, const ttk_loss_op* ops, const unsigned* tag_sets, const int* tag_code, ttk_stream_t stream) {
+  if (!tag_code) return ttk_loss_batch(nops, ops, stream);  // every row live
+  TTK_REQUIRE(nops > 0 && nops <= kBatchMax && ops && tag_sets, "loss_batch_rows: 1..%d ops", kBatchMax);
+  BatchArgs a{};
+  TagSets m{};
+  int items = 0;
+  for (int k = 0; k < nops; ++k) {
+    TTK_REQUIRE(ops[k].kind >= 0 && ops[k].kind < TTK_OP_COUNT && ops[k].items > 0, "loss_batch_rows: op %d: bad kind or item count", k);
+    a.op[k] = ops[k];
+    m.set[k] = tag_sets[k];
+    if (ops[k].items > items) items = ops[k].items;
+  }
+  hipLaunchKernelGGL(loss_batch_rows_k, dim3((unsigned)((items + 255) / 256), (unsigned)nops), dim3(256), 0, (hipStream_t)stream, a, m, tag_code);
+  TTK_LAUNCH_CHECK("loss_batch_rows");
+}
+int ttk_row_weights(const float* wtable, const int* tag_code, const float* dataset_weight, int K, int n, float* rw, ttk_stream_t stream) {
+  TTK_REQUIRE(wtable && tag_code && rw && K > 0 && n > 0 && (long long)K * n <= 0x7fffffffLL, "row_weights: bad arguments");
+  hipLaunchKernelGGL(row_weights_k, TTK_GRID(K * n), wtable, tag_code, dataset_weight, K, n, rw);
+  TTK_LAUNCH_CHECK("row_weights");
 }
 
 }  // extern "C"

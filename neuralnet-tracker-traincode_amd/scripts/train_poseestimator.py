@@ -178,8 +178,21 @@ def make_parser():
                    help="the crop's resampler in the train and the test loader: bilinear (four taps at the pixel centre) | area (the reference's "
                    "anti-aliased INTER_AREA crop: trackertraincode.datatransformation.gpu.GpuFocusRoiAugment)")
     p.add_argument("--graph-steps", default=False, action="store_true",
-                   help="single GPU: replay one captured hipGraph per training step instead of ~150 eager launches (train.GraphedTrainStep)")
+                   help="single GPU: replay one captured hipGraph per training step instead of ~150 eager launches (train.GraphedTrainStep).  With the "
+                   "default --graph-layout a graph holds for one per-Tag split and one set of loss weights: a --ds that mixes Tags (sizes drawn per "
+                   "step) falls back to eager steps after three misses, and --rampup-nll-losses re-captures at every epoch of the ramp")
+    p.add_argument("--graph-layout", default="per-tag", choices=["per-tag", "flat"], dest="graph_layout",
+                   help="with --graph-steps: per-tag (one graph per sub-batch layout) | flat (the step runs over all B rows with a Tag code per row and "
+                   "a device table of loss weights: ONE graph for any per-Tag split and through a weight ramp; train.flat_training_step).  "
+                   "Data-parallel runs stay eager either way")
     return p
+
+
+def graph_mode(args):
+    """fit()'s `graphed` argument: False without --graph-steps, else True (per-tag layout) or "flat"."""
+    if not getattr(args, "graph_steps", False):
+        return False
+    return "flat" if getattr(args, "graph_layout", "per-tag") == "flat" else True
 
 
 def main():
@@ -223,7 +236,7 @@ def main():
     try:
         train.fit(net, train_loader, train_crit, optimizer, scheduler, epochs=args.epochs, callbacks=callbacks,
                   val_loader=test_loader if rank == 0 else None, val_criterions=test_crit, reducer=reducer,
-                  graphed=bool(getattr(args, "graph_steps", False)) and reducer is None)
+                  graphed=graph_mode(args) if reducer is None else False)
     finally:
         parallel.install(None)
     if rank == 0:

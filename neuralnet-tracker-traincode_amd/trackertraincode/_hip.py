@@ -88,6 +88,8 @@ _SIGNATURES = {
     "ttk_loss_gmm_fwd": [_P, _P, _P, _P, _I, _D, _I, _P, _P],
     "ttk_loss_gmm_bwd": [_P, _P, _P, _P, _I, _D, _P, _I, _P],
     "ttk_loss_batch": [_I, _P],
+    "ttk_loss_batch_rows": [_I, _P, _P, _P],
+    "ttk_row_weights": [_P, _P, _P, _I, _I, _P],
     "ttk_blur3x3_fwd": [_P, _P, _I, _I, _I, _I, _I],
     "ttk_blur3x3_bwd": [_P, _P, _P, _I, _I, _I, _I, _I],
     "ttk_view_roi": [_P, _P, _P, _F, _I, _P],
@@ -122,7 +124,7 @@ _SIGNATURES = {
     "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 # Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the
@@ -228,29 +230,42 @@ class _Library:
             hint = "" if rc < 0 else " (a positive code is a hipError_t read from the sticky hipGetLastError(): an earlier launch of this step may have left it)"
             raise RuntimeError(f"{name} failed (code {rc}): {msg}{hint}")
 
-    def loss_batch(self, ops):
+    @staticmethod
+    def pack_loss_ops(chunk):
+        """[(entry point name, argument tuple as for call()), ...] -> ttk_loss_op array: the arguments go to p[] / i[] / f[] / d in signature order."""
+        arr = (LossOp * len(chunk))()
+        for o, (name, args) in zip(arr, chunk):
+            kind, items = LOSS_BATCH_OPS[name]
+            o.kind, o.items = kind, int(items(args))
+            np_ = ni = nf = 0
+            for ty, v in zip(_SIGNATURES[name], args):
+                if ty is _P:
+                    o.p[np_] = v
+                    np_ += 1
+                elif ty is _I:
+                    o.i[ni] = int(v)
+                    ni += 1
+                elif ty is _F:
+                    o.f[nf] = float(v)
+                    nf += 1
+                else:
+                    o.d = float(v)
+        return arr
+
+    def loss_batch(self, ops, tag_sets=None, tag_code=None):
         """ttk_loss_batch: `ops` = [(entry point name, argument tuple as for call()), ...], mutually independent; one launch
-        per LOSS_BATCH_MAX ops."""
+        per LOSS_BATCH_MAX ops.  With `tag_code` (int32 device tensor, one Tag code per row) and `tag_sets` (one 32-bit set of Tag
+        codes per op): ttk_loss_batch_rows - rows whose code is not in their op's set are dead (value and gradients 0, inputs unread)."""
+        if tag_code is not None and (tag_code.dtype != torch.int32 or tag_sets is None or len(tag_sets) != len(ops)):
+            raise RuntimeError("loss_batch: tag_code must be an int32 tensor and tag_sets must hold one set per op")
         for lo in range(0, len(ops), LOSS_BATCH_MAX):
             chunk = ops[lo:lo + LOSS_BATCH_MAX]
-            arr = (LossOp * len(chunk))()
-            for o, (name, args) in zip(arr, chunk):
-                kind, items = LOSS_BATCH_OPS[name]
-                o.kind, o.items = kind, int(items(args))
-                np_ = ni = nf = 0
-                for ty, v in zip(_SIGNATURES[name], args):
-                    if ty is _P:
-                        o.p[np_] = v
-                        np_ += 1
-                    elif ty is _I:
-                        o.i[ni] = int(v)
-                        ni += 1
-                    elif ty is _F:
-                        o.f[nf] = float(v)
-                        nf += 1
-                    else:
-                        o.d = float(v)
-            self.call("ttk_loss_batch", len(chunk), arr)
+            arr = self.pack_loss_ops(chunk)
+            if tag_code is None:
+                self.call("ttk_loss_batch", len(chunk), arr)
+            else:
+                sets = (ctypes.c_uint * len(chunk))(*[int(m) & 0xFFFFFFFF for m in tag_sets[lo:lo + LOSS_BATCH_MAX]])
+                self.call("ttk_loss_batch_rows", len(chunk), arr, sets, ptr(tag_code))
 
     def pwconv_prepared_bytes(self, cin: int, cout: int) -> int:
         return self.cdll.ttk_pwconv_prepared_bytes(cin, cout)

@@ -23,14 +23,19 @@ class _Batch:
     def __init__(self):
         self.ops, self.keep, self.records = [], [], []
         self.deferring = False  # set while a Function driven by apply() / BatchedLossFn runs: only ITS launches are deferred
+        # row liveness (train.flat_training_step): with `tag_code` (int32 [B] device tensor) the flush is ONE ttk_loss_batch_rows launch;
+        # every op then carries the Tag set that was current (`tag_set`) when it was collected
+        self.tag_code, self.tag_set, self.sets = None, ALL_TAGS, []
 
     def flush(self):
         ops, self.ops = self.ops, []
+        sets, self.sets = self.sets, []
         if ops:
-            _hip.lib().loss_batch(ops)
+            _hip.lib().loss_batch(ops, sets if self.tag_code is not None else None, self.tag_code)
         self.keep = []  # the launch is on the stream: the caching allocator may recycle the temporaries behind it
 
 
+ALL_TAGS = 0xFFFFFFFF
 _BATCHING = True  # False (set by tools / tests): one launch per loss op, the A/B of the batched launch
 _TLS = threading.local()  # the open batch of this thread (backward runs on autograd's worker thread)
 
@@ -79,7 +84,11 @@ def _call(name, *args):
     b = _batch()
     if b is not None and b.deferring and name in _hip.LOSS_BATCH_OPS:
         b.ops.append((name, args))
+        b.sets.append(b.tag_set)
         return
+    if b is not None and b.deferring and b.tag_code is not None:
+        # (ttk_loss_elem / _laplace / _rot_geodesic: single launches over all rows, dead ones included - no silent fallback)
+        raise NotImplementedError(f"{name} has no row-liveness form (it is not an op of ttk_loss_batch_rows): this loss cannot run in the flat step")
     _hip.lib().call(name, *args)
 
 
@@ -110,6 +119,7 @@ def apply(fn, *args):
             v = fn.forward(ctx, *args)
     finally:
         b.deferring = False
+    ctx.tag_set = b.tag_set
     b.records.append((fn, ctx, args, v))
     return v
 
@@ -128,6 +138,7 @@ class BatchedLossFn(Function):
         vals = [r[3] for r in records] + ordinary
         loss = WeightedSumFn.forward(ctx, scalars, sample_ws, scale, *vals)
         ctx.rec = (records, slots, n_inputs, len(ordinary))
+        ctx.tag_code = batch.tag_code
         return loss
 
     @staticmethod
@@ -136,8 +147,11 @@ class BatchedLossFn(Function):
         gvals = WeightedSumFn.backward(ctx, g)[3:]
         grads = [None] * n_inputs
         with loss_batch() as b:
-            b.deferring = True
-            outs = [fn.backward(fctx, gv) for (fn, fctx, _, _), gv in zip(records, gvals)]
+            b.deferring, b.tag_code = True, ctx.tag_code
+            outs = []
+            for (fn, fctx, _, _), gv in zip(records, gvals):
+                b.tag_set = fctx.tag_set  # the rows the forward op covered
+                outs.append(fn.backward(fctx, gv))
             b.deferring = False
             b.flush()
         for sl, out in zip(slots, outs):
@@ -487,6 +501,21 @@ class WeightedSumFn(Function):
             _call("ttk_weighted_sum_bwd", n, _p(g), (c_void_p * n)(*[_p(s) for s in sws[a:b]]), (c_float * n)(*scalars[a:b]),
                   (c_int * n)(*counts[a:b]), scale, (c_void_p * n)(*[_p(x) for x in gvals[a:b]]))
         return (None, None, None, *gvals)
+
+
+def row_weights(wtable: torch.Tensor, tag_code: torch.Tensor, dataset_weight, K: int) -> torch.Tensor:
+    """ttk_row_weights: rw[k, i] = wtable[k, tag_code[i]] * dataset_weight[i] for the K terms of the flat step, one launch.  wtable: float32
+    [K, 32] on the device, tag_code: int32 [B], dataset_weight: float32 [B] or None (= 1)."""
+    B = int(tag_code.shape[0])
+    if not (wtable.dtype == torch.float32 and wtable.numel() == 32 * K and tag_code.dtype == torch.int32 and tag_code.dim() == 1):
+        raise RuntimeError("row_weights: float32 [K, 32] weight table and int32 [B] Tag codes expected")
+    if dataset_weight is not None:
+        dataset_weight = _f32c(dataset_weight).reshape(-1)
+        if dataset_weight.numel() != B:
+            raise RuntimeError("row_weights: one dataset weight per row expected")
+    rw = torch.empty((K, B), dtype=torch.float32, device=tag_code.device)
+    _hip.lib().call("ttk_row_weights", _hip.ptr(wtable), _hip.ptr(tag_code), _hip.ptr(dataset_weight), K, B, _hip.ptr(rw))
+    return rw
 
 
 class PointsLossFn(Function):

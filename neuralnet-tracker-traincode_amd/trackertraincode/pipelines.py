@@ -103,10 +103,12 @@ def make_image_augmentations(generator: torch.Generator | None = None, whiten: b
 
 class SyntheticPoseLoader:
     """Endless iterator of `list[Batch]` split by Tag in fixed proportions (the contract of the train
-    loader returned by make_pose_estimation_loaders, reference :534-554)."""
+    loader returned by make_pose_estimation_loaders, reference :534-554).  vary_split=True: the per-Tag sizes are drawn anew every
+    step instead - a multinomial over the weights, seeded, summing to the batch size - as a loader over several datasets does
+    (datasets.resident.ResidentLoader); a Tag that draws no sample is left out of that step's list."""
 
     def __init__(self, batchsize: int, tags_and_weights: Sequence[tuple[Tag, float]], device="cuda", seed=1234, inputsize=129,
-                 steps_per_epoch: int | None = None, image_augmentations=None, single_batch: bool = False):
+                 steps_per_epoch: int | None = None, image_augmentations=None, single_batch: bool = False, vary_split: bool = False):
         # single_batch: the contract of the TEST loader instead (reference :543-552: one Batch per iteration, not a list) - one Tag only
         if single_batch and len(tags_and_weights) != 1:
             raise ValueError("single_batch: one Tag")
@@ -120,13 +122,28 @@ class SyntheticPoseLoader:
         self._gen = torch.Generator(device="cpu")
         self._gen.manual_seed(seed)
         self._steps = steps_per_epoch if steps_per_epoch is not None else (10 * 1024) // batchsize
+        self._vary = bool(vary_split)
+        if self._vary:
+            if single_batch:
+                raise ValueError("vary_split: a list of sub-batches per step, not single_batch")
+            # a generator of its own: the samples' stream is the one a fixed-split loader of this seed draws from
+            self._split_gen = torch.Generator(device="cpu")
+            self._split_gen.manual_seed(seed + 0x5117)
+            self._tags = [t for t, _ in tags_and_weights]
+            self._probs = torch.tensor([float(w) for _, w in tags_and_weights], dtype=torch.float64) / float(total)
+            self._batchsize = int(batchsize)
 
     def __len__(self):
         return self._steps
 
     def __iter__(self) -> Iterator[list[Batch]]:
         for _ in range(self._steps):
-            batches = [synthetic_subbatch(t, c, self._device, self._gen, self._inputsize) for t, c in self._plan]
+            plan = self._plan
+            if self._vary:
+                draws = torch.multinomial(self._probs, self._batchsize, replacement=True, generator=self._split_gen)
+                counts = torch.bincount(draws, minlength=len(self._tags)).tolist()
+                plan = [(t, c) for t, c in zip(self._tags, counts) if c > 0]
+            batches = [synthetic_subbatch(t, c, self._device, self._gen, self._inputsize) for t, c in plan]
             if self._augs:
                 for b in batches:
                     img = b["image"] + 0.5  # synthetic crops are stored whitened

@@ -16,6 +16,7 @@ detached DEVICE tensors (call .cpu() when you want them).
 from __future__ import annotations
 
 import ctypes
+import functools
 import itertools
 import math
 import os
@@ -28,7 +29,7 @@ from torch import Tensor
 from torch.optim.lr_scheduler import LambdaLR
 
 from . import _hip
-from .datasets.batch import Batch
+from .datasets.batch import Batch, Metadata
 from .neuralnets.io import save_model
 
 
@@ -494,6 +495,240 @@ def training_step(model: nn.Module, batches: List[Batch], epoch: int, criterions
     return {"loss": loss_sum, "mt_losses": by_name}
 
 
+# ---------------------------------------------------------------------------------------------
+# the step over ALL rows with per-row Tag codes ("flat" layout): launch arguments independent of the per-Tag split
+# ---------------------------------------------------------------------------------------------
+def _tag_code(tag) -> int:
+    code = int(getattr(tag, "value", tag))
+    if not 0 <= code < 32:
+        raise ValueError(f"Tag code {code} of {tag}: the row-liveness kernels take codes 0..31")
+    return code
+
+
+def flatten_batches(batches: List[Batch], fill: float = 0.0) -> Batch:
+    """The sub-batches of one step as ONE batch of B rows in sub-batch order.  Every tensor field becomes [B, ...]; rows whose
+    sub-batch lacks the field hold `fill` (0 in integer fields).  Added: `tag_code` (int32 [B], the value of each row's Tag) and
+    `dataset_weight` (float32 [B], 1 where a sub-batch had none).  Raises ValueError when the trailing shape or the dtype of a field
+    differs between sub-batches.  Works on CPU tensors too."""
+    if not batches:
+        raise ValueError("flatten_batches: no sub-batches")
+    sizes = [int(b.meta.prefixshape[0]) for b in batches]
+    B = sum(sizes)
+    spec: dict = {}
+    for b in batches:
+        for k, v in b.items():
+            if not torch.is_tensor(v):
+                continue
+            cur = (tuple(v.shape[1:]), v.dtype)
+            if spec.setdefault(k, cur) != cur:
+                raise ValueError(f"flatten_batches: field {k!r} is {cur[0]} {cur[1]} in {b} but {spec[k][0]} {spec[k][1]} in an earlier sub-batch")
+    device = next(v for v in batches[0].values() if torch.is_tensor(v)).device
+    out = {}
+    for k, (trail, dtype) in spec.items():
+        if k == "dataset_weight":
+            continue
+        if all(k in b for b in batches):
+            out[k] = torch.concat([b[k] for b in batches], dim=0)
+            continue
+        full = torch.full((B,) + trail, fill if dtype.is_floating_point else 0, dtype=dtype, device=device)
+        off = 0
+        for b, n in zip(batches, sizes):
+            if k in b:
+                full[off:off + n] = b[k]
+            off += n
+        out[k] = full
+    out["tag_code"] = torch.concat([torch.full((n,), _tag_code(b.meta.tag), dtype=torch.int32) for b, n in zip(batches, sizes)]).to(device)
+    out["dataset_weight"] = torch.concat([b["dataset_weight"].to(torch.float32).reshape(n) if "dataset_weight" in b
+                                          else torch.ones(n, dtype=torch.float32, device=device) for b, n in zip(batches, sizes)])
+    return Batch(Metadata(batches[0].meta._imagesize, batchsize=B, tag=None), out)
+
+
+class LossTerm(NamedTuple):
+    """One row of the flat term table: a criterion callable, its name (group prefixes included) and, per Tag whose criterion table
+    holds it, the weights along its path (innermost first; floats or functions of the epoch)."""
+    name: str
+    f: Callable[[Any, Any], Tensor]
+    paths: dict
+
+    @property
+    def tags(self):
+        return tuple(self.paths)
+
+    @property
+    def tag_set(self) -> int:
+        m = 0
+        for t in self.paths:
+            m |= 1 << _tag_code(t)
+        return m
+
+    def weight(self, tag, epoch) -> float:
+        """The product Criterion.evaluate / CriterionGroup.evaluate form for a sub-batch of `tag` at `epoch` (same order of the factors)."""
+        ws = [_weight_at(w, epoch) for w in self.paths[tag]]
+        out = ws[0]
+        for w in ws[1:]:
+            out = out * w
+        return out
+
+
+def loss_terms(criterions: dict) -> List[LossTerm]:
+    """The flat term table of a {Tag: CriterionGroup} dict: one term per distinct (name, criterion callable).  Two Criterions that
+    share a name but not the callable (Points3dLoss in 3D and in 2.5D) are two terms.  Order: first seen, walking the Tags' tables
+    from the one with the most terms down (ties in dict order) - the names then come out in the order concatenated_lossvals_by_name
+    gives for a step whose first sub-batch has the richest Tag, which is how the reference's loaders and goldens order them (a table
+    alone cannot know the order of a step's sub-batches)."""
+    if not isinstance(criterions, dict):
+        raise TypeError("loss_terms: a {Tag: CriterionGroup} dict is expected")
+    terms: dict = {}
+
+    def walk(c, tag, prefix, outer):
+        if isinstance(c, CriterionGroup):
+            for x in c.criterions:
+                walk(x, tag, prefix + c.name, (c.w,) + outer)
+            return
+        if not isinstance(c, Criterion):
+            raise NotImplementedError(f"loss_terms: {type(c).__name__} is neither a Criterion nor a CriterionGroup")
+        # (CriterionGroup.evaluate prepends its name to the names below it; the weights multiply from the criterion outwards)
+        key = (prefix + c.name, id(c.f))
+        term = terms.setdefault(key, LossTerm(key[0], c.f, {}))
+        if tag in term.paths:
+            raise NotImplementedError(f"loss term {key[0]!r} occurs twice in the criterion table of {tag}: one row cannot hold two values of a term")
+        term.paths[tag] = (c.w,) + outer
+
+    def leaves(c):
+        return sum(leaves(x) for x in c.criterions) if isinstance(c, CriterionGroup) else 1
+
+    for tag, c in sorted(criterions.items(), key=lambda kv: -leaves(kv[1])):  # (sorted() is stable)
+        walk(c, tag, "", ())
+    return list(terms.values())
+
+
+class FlatLoss:
+    """Device-side tables of the flat step for one criterion dict: the terms, their Tag sets and the [K, 32] table of weights per term
+    and Tag code, which is the only thing that changes with the epoch (`set_epoch` rewrites it with a copy - outside a captured graph,
+    like ClipAdam.sync_hyper_to_device)."""
+
+    def __init__(self, criterions, device):
+        self.terms = loss_terms(criterions)
+        if not self.terms:
+            raise ValueError("the criterion table has no terms")
+        self.names = list(dict.fromkeys(t.name for t in self.terms))
+        by_name = {n: [t for t in self.terms if t.name == n] for n in self.names}
+        for n, ts in by_name.items():
+            sets = [t.tag_set for t in ts]
+            if sum(bin(m).count("1") for m in sets) != bin(functools.reduce(lambda a, b: a | b, sets)).count("1"):
+                raise NotImplementedError(f"loss terms named {n!r} overlap in their Tags: one [B] vector cannot hold both")
+        name_sets = [functools.reduce(lambda a, b: a | b, [t.tag_set for t in by_name[n]]) for n in self.names]
+        # live[name][code]: whether a row of that Tag code carries the name's loss - one index_select with the row codes gives "mt_rows"
+        self.live = torch.tensor([[bool((m >> c) & 1) for c in range(32)] for m in name_sets], dtype=torch.bool, device=device)
+        self.wtable = torch.zeros((len(self.terms), 32), dtype=torch.float32, device=device)
+        self._epoch_sig = None
+
+    def table_at(self, epoch):
+        rows = []
+        for t in self.terms:
+            row = [0.0] * 32
+            for tag in t.paths:
+                row[_tag_code(tag)] = float(t.weight(tag, epoch))
+            rows.append(row)
+        return rows
+
+    def set_epoch(self, epoch, replaying=False) -> bool:
+        """Write the epoch's weights into the device table if they changed.  `replaying`: earlier replays of a captured step may still
+        read the old values - wait for them first (once per epoch at most)."""
+        rows = self.table_at(epoch)
+        sig = tuple(map(tuple, rows))
+        if sig == self._epoch_sig:
+            return False
+        if replaying:
+            torch.cuda.current_stream().synchronize()
+        self.wtable.copy_(torch.tensor(rows, dtype=torch.float32))  # synchronous, pageable: rare
+        self._epoch_sig = sig
+        return True
+
+
+class _MissingLabel(KeyError):
+    pass
+
+
+class _Labels:
+    """The flat batch as the criterions see it: a field no sub-batch of the step carries raises _MissingLabel."""
+
+    def __init__(self, batch: Batch):
+        self._batch, self.meta = batch, batch.meta
+
+    def __getitem__(self, k):
+        try:
+            return self._batch[k]
+        except KeyError:
+            raise _MissingLabel(k) from None
+
+    def __contains__(self, k):
+        return k in self._batch
+
+    def __getattr__(self, name):
+        return getattr(self._batch, name)
+
+
+def flat_training_step(model: nn.Module, flat_batch: Batch, epoch: int, criterions, _tables: "FlatLoss | None" = None):
+    """training_step over the B rows of `flatten_batches(...)`: the reference's sum (train.py:372-439) written as
+    (1/B) sum_terms sum_{i<B} [Tag_i has the term] * w_term,Tag_i(epoch) * dataset_weight_i * val_term,i.  Every term's kernel visits all
+    B rows and is told which are live (ttk_loss_batch_rows: membership of the row's Tag code in the term's Tag set, not the weight);
+    the weights come from a device table indexed by the Tag code (ttk_row_weights).  No launch argument depends on the per-Tag split.
+    Returns {"loss", "mt_losses": {name: [B] values, 0 in dead rows}, "mt_rows": {name: [B] bool, the live rows}}:
+    mt_losses[name][mt_rows[name]] is what training_step's mt_losses[name] holds for the same sub-batches.
+    A term whose label field is in none of the step's sub-batches (no field of that name in `flat_batch`) has no live row: its values
+    are zeros and its kernel is not launched."""
+    from .neuralnets import _hipops
+
+    image = flat_batch["image"]
+    if not image.is_cuda:
+        raise RuntimeError("flat_training_step runs in HIP kernels on the MI355X: CUDA tensors required (no CPU fallback)")
+    _hip.lib().clear_stale_error("the start of a training step")
+    tables = _tables if _tables is not None else FlatLoss(criterions, image.device)
+    if _tables is None:
+        tables.set_epoch(epoch)
+    tag_code = flat_batch["tag_code"]
+    B = int(tag_code.shape[0])
+    preds = model(image, flat_batch["coord_convention_id"])
+    rw = _hipops.row_weights(tables.wtable, tag_code, flat_batch["dataset_weight"] if "dataset_weight" in flat_batch else None, len(tables.terms))
+    vals = []
+    labels = _Labels(flat_batch)
+    with _hipops.loss_batch() as lb:
+        lb.tag_code = tag_code
+        for k, term in enumerate(tables.terms):
+            lb.tag_set = term.tag_set
+            seen = len(lb.records)
+            try:
+                v = term.f(preds, labels)
+            except _MissingLabel:
+                if len(lb.records) != seen:
+                    raise NotImplementedError(f"criterion {term.name!r} cannot be flattened: it launched a loss kernel before reading a label "
+                                              "that this step does not have") from None
+                continue  # no row of this step can be live for it
+            if not (len(lb.records) == seen + 1 and lb.records[-1][3] is v and tuple(v.shape) == (B,)):
+                # the value is not the untouched output of ONE batched loss kernel (the criterion post-processes it, combines several, or
+                # computes it elsewhere): default_compute_loss runs such terms unbatched, over their sub-batch's rows only - there is no
+                # such thing here, and computing over dead rows would read labels that do not exist
+                raise NotImplementedError(f"criterion {term.name!r} cannot be flattened: its value is not the direct per-sample output of one "
+                                          "batched loss kernel (use the per-Tag layout)")
+            vals.append(LossVal(v, SampleWeight(1.0, rw[k], v), term.name))
+    loss_sum = _batched_loss_sum(lb, vals, 1.0 / B)
+    if not vals:
+        raise ValueError("flat_training_step: the batch carries the labels of none of the loss terms")
+    by_name = defaultdict(list)
+    for v in vals:
+        by_name[v.name].append(v.val)
+    mt_losses = {}
+    for n in tables.names:
+        vs = by_name.get(n)
+        if not vs:
+            mt_losses[n] = torch.zeros(B, dtype=torch.float32, device=tag_code.device)
+        else:
+            mt_losses[n] = vs[0] if len(vs) == 1 else functools.reduce(torch.add, vs)  # (disjoint Tag sets: dead rows are exactly 0)
+    live = tables.live.index_select(1, tag_code)  # [names, B]; the codes are those of _tag_code, 0..31
+    return {"loss": loss_sum, "mt_losses": mt_losses, "mt_rows": dict(zip(tables.names, live.unbind(0)))}
+
+
 def _criterion_weights(c, step):
     """Flat tuple of every weight in a criterion tree at `step` (they are constants inside a captured graph)."""
     if isinstance(c, dict):
@@ -515,11 +750,25 @@ class GraphedTrainStep:
     learning-rate-independent launch arguments stay the same: `run()` compares a signature and re-captures when it
     changes (e.g. during the NLL ramp epochs).  Learning rates, weight decays and Adam's step count live in device
     memory (ClipAdam.sync_hyper_to_device), so scheduler steps need no re-capture.  New batches are copied into the
-    graph's static input tensors.  Single-GPU: the data-parallel all-reduce is issued eagerly (train.fit)."""
+    graph's static input tensors.  Single-GPU: the data-parallel all-reduce is issued eagerly (train.fit).
 
-    def __init__(self, model: nn.Module, criterions, optimizer: "ClipAdam"):
+    layout="flat": the captured step is `flat_training_step` over static [B, ...] buffers, whose launch arguments depend neither on
+    the per-Tag split nor on the criterion weights - per step the sub-batches' fields and one Tag code per row are copied in (one
+    ttk_multi_copy launch, no host synchronisation), on an epoch change the [terms, 32] weight table.  The signature is (B, the label
+    fields seen so far, model.training): ONE capture serves a run whose first step shows every field, a loader that mixes Tags and
+    draws their sizes anew every step included; otherwise a Tag that brings a new field re-captures once.  `run()` then also returns
+    "mt_rows" (flat_training_step)."""
+
+    def __init__(self, model: nn.Module, criterions, optimizer: "ClipAdam", layout: str = "per_tag"):
         if not isinstance(optimizer, ClipAdam):
             raise TypeError("GraphedTrainStep needs the fused ClipAdam optimiser (its step is capturable)")
+        if layout not in ("per_tag", "flat"):
+            raise ValueError(f"GraphedTrainStep: layout {layout!r} (per_tag | flat)")
+        self.layout = layout
+        self._flat: dict = {}       # flat layout: static [B, ...] buffer per field
+        self._fields: dict = {}     # flat layout: field -> (trailing shape, dtype), every field seen so far
+        self._codes: dict = {}      # flat layout: Tag code -> int32 [B] device tensor filled with it (source of the per-row codes)
+        self._tables = None         # flat layout: FlatLoss
         self.model, self.criterions, self.optimizer = model, criterions, optimizer
         self.graph = None
         self._sig = None
@@ -562,6 +811,8 @@ class GraphedTrainStep:
     def run(self, batches: List[Batch], epoch: int):
         """One training step.  Returns {"loss", "mt_losses"}; when replayed these are the graph's static output
         tensors (overwritten by the next call)."""
+        if self.layout == "flat":
+            return self._run_flat(batches, epoch)
         if self.eager_only:
             return self._eager(batches, epoch)
         sig = self._signature(batches, epoch)
@@ -603,6 +854,93 @@ class GraphedTrainStep:
         if fdst:
             _hip.lib().multi_copy(fsrc, fdst)
         self._miss_streak = 0
+        self.optimizer.before_graph_replay()
+        self.graph.replay()
+        self.optimizer.after_graph_replay()
+        return self._out
+
+    # ---- flat layout ---------------------------------------------------------------------------------------------------------------
+    def _flat_fields(self, batches):
+        """Adds the tensor fields of `batches` to the fields seen so far; ValueError when a field disagrees with what was seen."""
+        for b in batches:
+            for k, v in b.items():
+                if torch.is_tensor(v) and k != "tag_code":
+                    cur = (tuple(v.shape[1:]), v.dtype)
+                    if self._fields.setdefault(k, cur) != cur:
+                        raise ValueError(f"GraphedTrainStep(flat): field {k!r} is {cur[0]} {cur[1]} in {b}, {self._fields[k][0]} {self._fields[k][1]} before")
+
+    def _flat_copy_in(self, batches):
+        """The sub-batches' fields and Tag codes -> rows of the static buffers: every 32-bit-word tensor in one ttk_multi_copy launch."""
+        as_words = lambda t: t if t.dtype == torch.float32 else t.view(torch.float32)
+        fsrc, fdst = [], []
+        off = 0
+        for b in batches:
+            n = int(b.meta.prefixshape[0])
+            code = _tag_code(b.meta.tag)
+            if code not in self._codes:  # (first sight of a Tag: one allocation and fill, outside any capture)
+                self._codes[code] = torch.full((self._B,), code, dtype=torch.int32, device=self._flat["tag_code"].device)
+            items = [("tag_code", self._codes[code][:n])] + [(k, v) for k, v in b.items() if torch.is_tensor(v) and k != "tag_code"]
+            if "dataset_weight" not in b:
+                items.append(("dataset_weight", self._ones[:n]))
+            for k, v in items:
+                d = self._flat[k][off:off + n]
+                if v.dtype != d.dtype and k == "dataset_weight":
+                    v = v.to(d.dtype)
+                if v.is_cuda and v.dtype == d.dtype and v.element_size() % 4 == 0 and v.is_contiguous() and v.numel() == d.numel() and v.data_ptr() % 4 == 0:
+                    if v.numel():
+                        fsrc.append(as_words(v.reshape(n, -1)))
+                        fdst.append(as_words(d.reshape(n, -1)))
+                else:
+                    d.copy_(v.reshape(d.shape), non_blocking=True)
+            off += n
+        if fdst:
+            _hip.lib().multi_copy(fsrc, fdst)
+
+    def _flat_eager(self, batches, epoch):
+        self.optimizer.zero_grad(set_to_none=True)
+        self._tables.set_epoch(epoch, replaying=self.graph is not None)
+        out = flat_training_step(self.model, flatten_batches(batches), epoch, self.criterions, self._tables)
+        out["loss"].backward()
+        self.optimizer.step()
+        return out
+
+    def _run_flat(self, batches: List[Batch], epoch: int):
+        B = sum(int(b.meta.prefixshape[0]) for b in batches)
+        dev = batches[0]["image"].device
+        if self._tables is None:
+            self._tables = FlatLoss(self.criterions, dev)
+        known = len(self._fields)
+        self._flat_fields(batches)
+        sig = (B, self.model.training)
+        if sig != self._sig or len(self._fields) != known:
+            # first step with this batch size / a Tag that brings a field no earlier step had: run it eagerly (lazy initialisation, table
+            # building), then capture over static buffers that hold every field seen so far
+            out = self._flat_eager(batches, epoch)
+            out = {"loss": out["loss"].detach().clone(), "mt_losses": {k: v.detach().clone() for k, v in out["mt_losses"].items()},
+                   "mt_rows": {k: v.clone() for k, v in out["mt_rows"].items()}}
+            torch.cuda.synchronize()
+            self._B = B
+            self._flat = {k: torch.zeros((B,) + trail, dtype=dtype, device=dev) for k, (trail, dtype) in self._fields.items() if k != "dataset_weight"}
+            self._flat["tag_code"] = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._flat["dataset_weight"] = torch.ones(B, dtype=torch.float32, device=dev)
+            self._ones = torch.ones(B, dtype=torch.float32, device=dev)
+            self._codes = {}
+            self._flat_copy_in(batches)
+            static = Batch(Metadata(batches[0].meta._imagesize, batchsize=B, tag=None), self._flat)
+            self.optimizer.sync_hyper_to_device()
+            self.graph = torch.cuda.CUDAGraph()
+            self.optimizer.zero_grad(set_to_none=True)
+            with _hip.CAPTURE_LOCK:
+                with torch.cuda.graph(self.graph):  # one stream, no forks
+                    captured = flat_training_step(self.model, static, epoch, self.criterions, self._tables)
+                    captured["loss"].backward()
+                    self.optimizer.step()
+            self._out = captured
+            self.captures += 1
+            self._sig = sig
+            return out
+        self._flat_copy_in(batches)
+        self._tables.set_epoch(epoch, replaying=True)
         self.optimizer.before_graph_replay()
         self.graph.replay()
         self.optimizer.after_graph_replay()
@@ -684,12 +1022,16 @@ def fit(model: nn.Module, train_loader, criterions, optimizer, scheduler=None, e
     older hook form of the same (runs between backward and the optimiser step).
     Gradients are dropped (set_to_none) before every step: the arena views autograd installs are the exchange buffers.
     `graphed=True` (single replica, ClipAdam): every step is a replay of ONE captured hipGraph (`GraphedTrainStep`; re-captured when the
-    sub-batch layout or the epoch's loss weights change); `on_step` then receives the graph's static output tensors."""
+    sub-batch layout or the epoch's loss weights change); `on_step` then receives the graph's static output tensors.
+    `graphed="flat"`: the same with GraphedTrainStep's flat layout - one graph also when the per-Tag sizes change from step to step and
+    through the epochs of a weight ramp; `on_step` receives [B] loss vectors and their live-row masks ("mt_rows")."""
     stepper = None
     if graphed:
+        if isinstance(graphed, str) and graphed != "flat":
+            raise ValueError(f"fit: graphed={graphed!r} (False | True | 'flat')")
         if reducer is not None or grad_sync is not None:
             raise ValueError("graphed steps are single-replica (collectives inside a captured graph are untested on this stack)")
-        stepper = GraphedTrainStep(model, criterions, optimizer)
+        stepper = GraphedTrainStep(model, criterions, optimizer, layout="flat" if graphed == "flat" else "per_tag")
     for cb in callbacks:
         if hasattr(cb, "on_train_start"):
             cb.on_train_start(model)
