@@ -1,5 +1,5 @@
-// Backward of the first pointwise convolutions (32 -> 64, 64 -> 128 and - second half of this file - 128 -> 128 channels; DepthWiseBlock.conv_sep + bn_sep,
-// backbones/mobilenet_v1.py:67-68,82-84) as ONE kernel: data gradient and weight gradient from one read of the operands.
+// Backward of the first pointwise convolutions (32 -> 64, 64 -> 128 and - second half of this file - 128 -> 128 channels, then 128 -> 256 and
+// 256 -> 256 under another register and LDS plan; DepthWiseBlock.conv_sep + bn_sep, backbones/mobilenet_v1.py:67-68,82-84) as ONE kernel: data gradient and weight gradient from one read of the operands.
 //
 // These layers have the largest activations of the network and are HBM-bound.  As two kernels (pwconv.hip: pw_gemm_k
 // in data-gradient mode, pw_wgrad_k) the gradient g and the raw output y of the convolution (2 x M x Cout floats) and the
@@ -529,17 +529,295 @@ pw_bwd_fused16_k(const float* __restrict__ g, const float* __restrict__ y, const
   }
 }
 
-// 128 -> 128 always runs on the fp16 pipe; 64 -> 128 too when the prepared block holds fp16 planes (default TTK_GEMM mode), else
-// on fp32 MFMA from the raw weights
-static bool fused_f16(int Cin) { return Cin == 128 || (Cin == 64 && gemm_mode() == GEMM_F16X2 && !exp_env("TTK_FUSED_FP32")); }
-static bool fused_shape(int Cin, int Cout) {
-  // (the 128 -> 128 form reads the fp16 planes of the prepared weight block: default TTK_GEMM mode only)
-  return (Cin == 32 && Cout == 64) || (Cin == 64 && Cout == 128) || (Cin == 128 && Cout == 128 && gemm_mode() == GEMM_F16X2);
+// ---------------------------------------------------------------------------------------------------------------------
+// The layers with 256 output channels (128 -> 256, and 256 -> 256 as two workgroups per row tile that take 128 input channels
+// each): the arithmetic of the kernel above under another register and LDS plan.  With 256 output channels the weight planes
+// of a 32-channel ci tile (128 VGPRs) and its weight-gradient accumulators (128) no longer fit one wave, and a stage that
+// holds dy in two layouts takes 97 KB.  Here
+//  * all eight waves stage AND multiply; wave w owns the 16 input channels 16 w .. 16 w + 15 of the workgroup's 128 for both
+//    products on v_mfma_f32_16x16x32_f16: W^T fragments 8 k32 steps x 2 planes = 64 VGPRs (cut from the raw weights once per
+//    workgroup, as the 64 -> 128 form does), weight-gradient accumulators 16 co tiles x 4 = 64, data-gradient accumulators 8;
+//  * dy lies in LDS ONCE, row-major, as two [32 rows][128 co] images of 256-byte rows whose 16-byte chunks are XORed with
+//    ((row & 3) << 2) | ((row >> 2) & 3): the data gradient reads rows (ds_read_b128, k = co), the weight gradient reads the same
+//    image with the transposing ds_read_b64_tr_b16 (k = rows: lane group g takes rows 8 g .. 8 g + 7 of a 16-co block);
+//  * a = relu(bn_dw(ydw)) lies transposed [ci][32 rows] (64-byte rows, chunk XOR (ci >> 2) & 3), ydw - mean in fp32 for the
+//    epilogue: a stage is 32 + 16 + 16.5 KB, double-buffered.
+// A thread loads 4 rows x 4 output channels of g and y (threads 0 .. 255 also 4 x 4 of ydw) one tile ahead of the tile it
+// stores to LDS, two ahead of the tile the workgroup multiplies: the loads stay in flight under the MFMAs of a whole stage.
+typedef short fzs16x4 __attribute__((ext_vector_type(4)));
+typedef short fzs16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kWideCW = 128;  // input channels per workgroup
+struct WideShape {
+  static constexpr int COUT = 256;
+  static constexpr int DyPlane = kF16BM * COUT * 2;   // bytes of one piece plane of dy (two 8 KB images of 128 co)
+  static constexpr int APlane = kWideCW * kF16BM * 2;  // ... of a, transposed
+  static constexpr int Ldc = kWideCW + 4;
+  static constexpr int Stage = 2 * DyPlane + 2 * APlane + kF16BM * Ldc * 4;
+};
+
+// base pointer + 32-bit BYTE offset: the address stays one scalar base and one VGPR (an element offset would be widened to 64 bits)
+template <typename T> __device__ __forceinline__ T* wide_at(T* p, unsigned byte_off) {
+  return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + byte_off);
+}
+__device__ __forceinline__ int wide_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+
+__device__ __forceinline__ fz16x8 wide_tr_frag(const unsigned char* p0, const unsigned char* p1) {
+  // rows 8 g .. 8 g + 3 and 8 g + 4 .. 8 g + 7 of a 16-channel block (the lane's addresses hold its row q and channel quad p):
+  // element j = the lane's channel at row 8 g + j
+  const fzs16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fzs16x4*)(p0));
+  const fzs16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fzs16x4*)(p1));
+  const fzs16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(fz16x8, v);
 }
 
-static int fused_grid(int64_t M, int Cin) {
+// CINT = 128: workgroup b walks the row tiles b, b + grid, ..  CINT = 256: `walkers` = grid / 2 pairs of workgroups; the two
+// halves of a pair (input channels 0 .. 127 | 128 .. 255) walk the same tiles and both read all of dy.  Workgroup ids i and i + 8
+// land on one XCD, so the pair of walker j is (16 (j / 8) + j % 8, + 8): the second read of a tile finds it in that XCD's L2.
+template <int CINT>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ bn_pw, const float* __restrict__ wraw,
+                  const float* __restrict__ wmax, const float* __restrict__ ydw, const float* __restrict__ bn_dw, float* __restrict__ g_dw,
+                  float* __restrict__ dW, float* __restrict__ wpartial, float* __restrict__ part, int64_t M, int ntiles) {
+  using S_ = WideShape;
+  constexpr int BM = kF16BM, COUT = S_::COUT, CW = kWideCW, kStage = S_::Stage, kDyP = S_::DyPlane, kAP = S_::APlane, kLdc = S_::Ldc;
+  constexpr int HALVES = CINT / CW;
+  static_assert(CINT == 128 || CINT == 256, "shapes");
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kStage + (4 * COUT + 3 * CW + 2 * 512) * 4];
+  // BatchNorm constants of the staging role, scaled: read from LDS per tile (held in registers they are 28 VGPRs through the MFMA phase)
+  float* cpw = reinterpret_cast<float*>(lds + 2 * kStage);   // [ga sa][gb sa][gmean][mean of bn_pw][COUT]
+  float* cdw = cpw + 4 * COUT;     // [scale sx][beta sx][mean of bn_dw][CW]
+  float* acc12 = cdw + 3 * CW;     // [2][512]: every lane's sums of g_dw and g_dw (ydw - mean)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n16 = lane & 15, grp = lane >> 4;
+  // The roles below take their lane-derived offsets from a thread id the compiler cannot see through, once per tile: held across the
+  // whole loop instead, the offsets of all three roles (about 20 registers) are live at every point and the kernel spills.
+  auto fresh_tid = [&]() { int v = tid; asm volatile("" : "+v"(v)); return v; };
+  int walker = blockIdx.x, cio = 0, nwalk = gridDim.x;
+  if (HALVES == 2) {
+    nwalk = gridDim.x >> 1;
+    const int b = blockIdx.x, b0 = (nwalk & ~7) * 2;  // whole groups of 8 pairs; the rest pairs neighbours
+    walker = b < b0 ? (b >> 4) * 8 + (b & 7) : (nwalk & ~7) + ((b - b0) >> 1);
+    cio = (b < b0 ? (b >> 3) & 1 : (b - b0) & 1) * CW;
+  }
+  // (uniform values, moved to scalar registers)
+  auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+  const float sa = uni(pow2_scale(bn_pw[(size_t)TTK_BN_AUX * COUT + TTK_AUX_DY_BOUND]));
+  const float sx = uni(pow2_scale(bn_dw[(size_t)TTK_BN_AUX * CINT + TTK_AUX_ACT_BOUND]));
+  const float sw = uni(pow2_scale(*wmax));
+
+  for (int i = tid; i < COUT; i += 512) {
+    cpw[i] = bn_pw[TTK_BN_GA * COUT + i] * sa;
+    cpw[COUT + i] = bn_pw[TTK_BN_GB * COUT + i] * sa;
+    cpw[2 * COUT + i] = bn_pw[TTK_BN_GMEAN * COUT + i];
+    cpw[3 * COUT + i] = bn_pw[TTK_BN_MEAN * COUT + i];
+  }
+  for (int i = tid; i < CW; i += 512) {
+    cdw[i] = bn_dw[TTK_BN_SCALE * CINT + cio + i] * sx;
+    cdw[CW + i] = bn_dw[TTK_BN_BETA * CINT + cio + i] * sx;
+    cdw[2 * CW + i] = bn_dw[TTK_BN_MEAN * CINT + cio + i];
+  }
+  __syncthreads();
+
+  // ---- staging role: g and y: rows 4 mb .. 4 mb + 3, output channels 4 cq .. 4 cq + 3; ydw: rows 2 rp, 2 rp + 1, input channels
+  // cio + 4 cqa .. (a wave covers whole 128-byte rows of one channel block).  Offsets are 32-bit: the launch holds M * 256 below 2^30.
+  const unsigned Mu = (unsigned)M;
+  fz32x4 rg[4], ry[4], rc[2];
+  auto load = [&](int t) {
+    const int ft = fresh_tid(), mb = ft & 7, cq = ft >> 3, rp = (wave & 1) * 8 + ((ft & 63) >> 3), cqa = (wave >> 1) * 8 + (ft & 7);
+    const unsigned r0 = (unsigned)t * BM + 4 * mb, q0 = (unsigned)t * BM + 2 * rp;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned row = r0 + i < Mu ? r0 + i : Mu - 1;
+      const unsigned off = (((cq >> 3) * Mu + row) * kCB + 4 * (cq & 7)) * 4;  // activations: channel blocks (ttk_common.h)
+      const float4 a = ld4nt(wide_at(g, off)), b = ld4nt(wide_at(y, off));
+      rg[i] = fz32x4{a.x, a.y, a.z, a.w}; ry[i] = fz32x4{b.x, b.y, b.z, b.w};
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const unsigned row = q0 + i < Mu ? q0 + i : Mu - 1;
+      const float4 c = ld4(wide_at(ydw, ((((cio >> 5) + (cqa >> 3)) * Mu + row) * kCB + 4 * (cqa & 7)) * 4));  // (read again by the depthwise backward: cached)
+      rc[i] = fz32x4{c.x, c.y, c.z, c.w};
+    }
+  };
+  auto store = [&](int t, int st) {
+    const int ft = fresh_tid(), mb = ft & 7, cq = ft >> 3, rp = (wave & 1) * 8 + ((ft & 63) >> 3), cqa = (wave >> 1) * 8 + (ft & 7);
+    const int dyoff = (cq >> 5) * (kDyP / 2) + 4 * mb * 256 + (((((cq & 31) >> 1) ^ (mb & 3))) << 4) + (cq & 1) * 8;  // 8-byte piece cq of row 4 mb
+    unsigned char* S = lds + st * kStage;
+    unsigned char* DyR = S;
+    unsigned char* AT = S + 2 * kDyP;
+    float* Yc = reinterpret_cast<float*>(AT + 2 * kAP);
+    const unsigned r0 = (unsigned)t * BM + 4 * mb, q0 = (unsigned)t * BM + 2 * rp;
+    {
+      const fz32x4 dsc = *reinterpret_cast<const fz32x4*>(cdw + 4 * cqa), dbe = *reinterpret_cast<const fz32x4*>(cdw + CW + 4 * cqa);
+      const fz32x4 dmean = *reinterpret_cast<const fz32x4*>(cdw + 2 * CW + 4 * cqa);
+      fz32x4 av[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const fz32x4 yc = rc[i] - dmean;
+        fz32x4 a = dsc * yc + dbe;
+        a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
+        if (q0 + i >= Mu) a = fz32x4{0.f, 0.f, 0.f, 0.f};  // rows past the end contribute nothing
+        av[i] = a;
+        *reinterpret_cast<fz32x4*>(Yc + (2 * rp + i) * kLdc + 4 * cqa) = yc;
+      }
+      // transposed: channel 4 cqa + e, rows 2 rp, 2 rp + 1 (k) -> 4 bytes per plane
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const fz32x2 v{av[0][e], av[1][e]};
+        const fz16x2 vh = __builtin_convertvector(v, fz16x2);
+        const fz16x2 vl = __builtin_convertvector(v - __builtin_convertvector(vh, fz32x2), fz16x2);
+        const int offa = (4 * cqa + e) * 64 + ((((rp >> 2) ^ (cqa & 3))) << 4) + (rp & 3) * 4;
+        *reinterpret_cast<unsigned*>(AT + offa) = __builtin_bit_cast(unsigned, vh);
+        *reinterpret_cast<unsigned*>(AT + kAP + offa) = __builtin_bit_cast(unsigned, vl);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const fz32x4 ga = *reinterpret_cast<const fz32x4*>(cpw + 4 * cq), gb = *reinterpret_cast<const fz32x4*>(cpw + COUT + 4 * cq);
+    const fz32x4 gmean = *reinterpret_cast<const fz32x4*>(cpw + 2 * COUT + 4 * cq), ymean = *reinterpret_cast<const fz32x4*>(cpw + 3 * COUT + 4 * cq);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      fz32x4 dy = ga * (rg[i] - gmean) + gb * (ry[i] - ymean);
+      if (r0 + i >= Mu) dy = fz32x4{0.f, 0.f, 0.f, 0.f};
+      uint2 ph, pl;
+      fz_split(dy, ph, pl);
+      // row 4 mb + i: wide_swz(row) = (i << 2) | (mb & 3)
+      const int off = (dyoff ^ (i << 6)) + i * 256;
+      *reinterpret_cast<uint2*>(DyR + off) = ph;
+      *reinterpret_cast<uint2*>(DyR + kDyP + off) = pl;
+      __builtin_amdgcn_sched_barrier(0);  // row by row: interleaving the four rows costs 20 more registers than the kernel has
+    }
+  };
+
+  // ---- multiplying role: input channel ci (of the workgroup's 128) on the lane, lane group grp = k octet / row quad
+  const int cil = 16 * wave + n16, ci = cio + cil;
+  fz16x8 Wf[COUT / 32][2];  // B fragments of the data gradient: W^T, k32 step s: co 32 s + 8 grp + j
+#pragma unroll
+  for (int s = 0; s < COUT / 32; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xs = wraw[(size_t)(32 * s + 8 * grp + e) * CINT + ci] * sw;
+      const _Float16 hh = (_Float16)xs;
+      Wf[s][0][e] = hh;
+      Wf[s][1][e] = (_Float16)(xs - (float)hh);
+    }
+  const float inv_dg = uni(1.f / (sa * sw)), inv_wg = uni(1.f / (sa * sx));
+  fz32x4 wacc[COUT / 16];
+#pragma unroll
+  for (int ct = 0; ct < COUT / 16; ++ct) wacc[ct] = fz32x4{0.f, 0.f, 0.f, 0.f};
+  // (the BatchNorm-backward sums of the epilogue are kept per lane in LDS, the ReLU constants read from cdw - their power-of-two scale
+  // leaves the sign alone: six registers that the kernel does not have)
+  acc12[tid] = 0.f; acc12[512 + tid] = 0.f;
+  auto compute = [&](int st, int t) {
+    const int ft = fresh_tid(), n16 = ft & 15, grp = (ft & 63) >> 4, cil = 16 * wave + n16, ci = cio + cil;
+    // byte offsets inside a dy plane.  Row read (row n16 [+ 16], 16-byte chunk 4 (s & 3) + grp of image s >> 2): XOR 64 (s & 3);
+    // transposed read (rows 8 grp + q [+ 4], channels 4 p .. of block ct: chunk 2 (ct & 7) + (p >> 1) of image ct >> 3): XOR 32 (ct & 7)
+    const int rbase = n16 * 256 + ((grp ^ wide_swz(n16)) << 4);
+    const int tq = n16 >> 2, tp = n16 & 3;
+    const int tb0 = (8 * grp + tq) * 256 + ((((tp >> 1) ^ wide_swz(8 * grp + tq))) << 4) + (tp & 1) * 8;
+    // (rows 8 grp + tq + 4: wide_swz is that of row 8 grp + tq with bit 0 set - the same register, XOR 16, + 4 rows)
+    const int aoff = cil * 64 + ((grp ^ ((cil >> 2) & 3)) << 4);
+    const unsigned char* S = lds + st * kStage;
+    const unsigned char* DyR = S;
+    const unsigned char* AT = S + 2 * kDyP;
+    const float* Yc = reinterpret_cast<const float*>(AT + 2 * kAP);
+    const unsigned m0 = (unsigned)t * BM;
+    // ---- data gradient: 32 rows x this wave's 16 ci, contraction over the 256 co
+    fz32x4 acc[2] = {fz32x4{0.f, 0.f, 0.f, 0.f}, fz32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int s = 0; s < COUT / 32; ++s)
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const int off = (rbase ^ (64 * (s & 3))) + (s >> 2) * (kDyP / 2) + rt * 16 * 256;
+        const fz16x8 ah = *reinterpret_cast<const fz16x8*>(DyR + off), al = *reinterpret_cast<const fz16x8*>(DyR + kDyP + off);
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, Wf[s][1], acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, Wf[s][0], acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, Wf[s][0], acc[rt], 0, 0, 0);
+      }
+    // ---- weight gradient: dW[co block ct][this wave's 16 ci] += dy^T a over the 32 rows (one k32 step)
+    const fz16x8 bh = *reinterpret_cast<const fz16x8*>(AT + aoff), bl = *reinterpret_cast<const fz16x8*>(AT + kAP + aoff);
+#pragma unroll
+    for (int ct = 0; ct < COUT / 16; ++ct) {
+      const int o0 = (tb0 ^ (32 * (ct & 7))) + (ct >> 3) * (kDyP / 2), o1 = (tb0 ^ (32 * (ct & 7) ^ 16)) + (ct >> 3) * (kDyP / 2) + 4 * 256;
+      const fz16x8 ah = wide_tr_frag(DyR + o0, DyR + o1), al = wide_tr_frag(DyR + kDyP + o0, DyR + kDyP + o1);
+      wacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, wacc[ct], 0, 0, 0);
+      wacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, wacc[ct], 0, 0, 0);
+      wacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, wacc[ct], 0, 0, 0);
+    }
+    // ---- data-gradient epilogue: accumulator element r of lane (n16, grp) of row tile rt = row 16 rt + 4 grp + r, column ci
+    const float dsc1 = cdw[cil], dbe1 = cdw[CW + cil];
+    float s1 = acc12[tid], s2 = acc12[512 + tid];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * rt + 4 * grp + r;
+        const float yc = Yc[row * kLdc + cil];
+        const float out = fmaf(dsc1, yc, dbe1) > 0.f ? acc[rt][r] * inv_dg : 0.f;
+        if (m0 + row < Mu) {
+          *wide_at(g_dw, (((ci >> 5) * Mu + m0 + row) * kCB + (ci & 31)) * 4) = out;
+          s1 += out;
+          s2 = fmaf(out, yc, s2);
+        }
+      }
+    acc12[tid] = s1; acc12[512 + tid] = s2;
+  };
+
+  int t = walker;
+  if (t < ntiles) {
+    load(t);
+    store(t, 0);
+    if (t + nwalk < ntiles) load(t + nwalk);
+  }
+  __syncthreads();
+  for (int it = 0; t < ntiles; t += nwalk, ++it) {
+    const int tn = t + nwalk;
+    if (tn < ntiles) {
+      store(tn, (it + 1) & 1);
+      if (tn + nwalk < ntiles) load(tn + nwalk);  // lands under the MFMAs below
+    }
+    compute(it & 1, t);
+    __syncthreads();
+  }
+  // ---- the workgroup's share of dW: one atomicAdd per element (or, deterministic mode, its columns of the walker's slice)
+#pragma unroll
+  for (int ct = 0; ct < COUT / 16; ++ct)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int co = 16 * ct + 4 * grp + r;
+      const float v = wacc[ct][r] * inv_wg;
+      if (wpartial) wpartial[(size_t)walker * COUT * CINT + co * CINT + ci] = v;
+      else atomicAdd(dW + co * CINT + ci, v);
+    }
+  // ---- BatchNorm-backward sums: the four lane groups of channel c's wave, in a fixed order (the loop's last barrier published acc12)
+  if (part && tid < 2 * CW) {
+    const int which = tid / CW, c = tid % CW;
+    const float* src = acc12 + which * 512 + 64 * (c >> 4) + (c & 15);
+    part[(size_t)walker * 2 * CINT + which * CINT + cio + c] = (src[0] + src[16]) + (src[32] + src[48]);
+  }
+}
+
+// 128 -> 128, 128 -> 256 and 256 -> 256 always run on the fp16 pipe; 64 -> 128 too when the prepared block holds fp16 planes (default
+// TTK_GEMM mode), else on fp32 MFMA from the raw weights
+static bool fused_f16(int Cin) { return Cin == 128 || Cin == 256 || (Cin == 64 && gemm_mode() == GEMM_F16X2 && !exp_env("TTK_FUSED_FP32")); }
+// (experiment builds: TTK_FUSED_WIDE=0 routes both layers to the two kernels, =128 / =256 only that input width to the fused one)
+static bool fused_wide(int Cin, int Cout) {
+  static const int only = [] { const char* e = exp_env("TTK_FUSED_WIDE"); return e ? atoi(e) : -1; }();
+  return Cout == 256 && (Cin == 128 || Cin == 256) && (only < 0 || only == Cin);
+}
+constexpr int64_t kWideMaxM = ((int64_t)1 << 30) / 256 - kF16BM;  // 32-bit element offsets in pw_bwd_fused16w_k (past it: the two kernels)
+static bool fused_shape(int Cin, int Cout) {
+  // (the forms with 128 and more input channels take the |w| scale of the prepared weight block: default TTK_GEMM mode only)
+  return (Cin == 32 && Cout == 64) || (Cin == 64 && Cout == 128) ||
+         (((Cin == 128 && Cout == 128) || fused_wide(Cin, Cout)) && gemm_mode() == GEMM_F16X2);
+}
+
+// workgroups that walk the row tiles = rows of `part` = slices of the deterministic weight gradient (256 -> 256 launches two
+// workgroups per walker)
+static int fused_grid(int64_t M, int Cin, int Cout) {
   const int64_t ntiles = ceil_div(M, fused_f16(Cin) ? kF16BM : kFusedBM);
-  const int64_t cap = Cin == 32 ? 512 : 256;  // two workgroups per CU fit for the 32 -> 64 layer (62 KB of LDS), one for the others
+  // two workgroups per CU fit for the 32 -> 64 layer (62 KB of LDS), one for the others
+  const int64_t cap = Cin == 32 ? 512 : (fused_wide(Cin, Cout) && Cin == 256 ? 128 : 256);
   return (int)(ntiles < cap ? ntiles : cap);
 }
 
@@ -549,20 +827,22 @@ using namespace ttk;
 
 extern "C" {
 
-int ttk_pwconv1x1_bwd_fused_rows(int64_t M, int Cin, int Cout) { return fused_shape(Cin, Cout) && M > 0 ? fused_grid(M, Cin) : 0; }
+static bool fused_ok(int64_t M, int Cin, int Cout) { return fused_shape(Cin, Cout) && M > 0 && !(fused_wide(Cin, Cout) && M > kWideMaxM); }
+
+int ttk_pwconv1x1_bwd_fused_rows(int64_t M, int Cin, int Cout) { return fused_ok(M, Cin, Cout) ? fused_grid(M, Cin, Cout) : 0; }
 
 size_t ttk_pwconv1x1_bwd_fused_partial_bytes(int64_t M, int Cin, int Cout) {
-  return fused_shape(Cin, Cout) && M > 0 ? (size_t)fused_grid(M, Cin) * Cin * Cout * sizeof(float) : 0;
+  return fused_ok(M, Cin, Cout) ? (size_t)fused_grid(M, Cin, Cout) * Cin * Cout * sizeof(float) : 0;
 }
 
 int ttk_pwconv1x1_bwd_fused(const float* g, const float* y, const float* bn_pw, const float* w, const void* wsplit, const float* ydw,
                             const float* bn_dw, float* g_dw, float* dw, float* partial, float* part, int64_t M, int Cin, int Cout,
                             ttk_stream_t stream) {
   TTK_REQUIRE(g && y && bn_pw && ydw && bn_dw && g_dw && dw, "pwconv1x1_bwd_fused: null pointer");
-  TTK_REQUIRE(fused_shape(Cin, Cout) && M > 0, "pwconv1x1_bwd_fused: only the 32 -> 64, 64 -> 128 and 128 -> 128 layers (got %d -> %d)", Cin, Cout);
-  TTK_REQUIRE((Cin == 128 || w) && (!fused_f16(Cin) || wsplit),
-              "pwconv1x1_bwd_fused: the fp16 forms (128 -> 128; 64 -> 128 in the default mode) need the prepared weight block, 32 -> 64 and 64 -> 128 the raw weights");
-  const int ntiles = (int)ceil_div(M, fused_f16(Cin) ? kF16BM : kFusedBM), grid = fused_grid(M, Cin);
+  TTK_REQUIRE(fused_ok(M, Cin, Cout), "pwconv1x1_bwd_fused: only the 32 -> 64, 64 -> 128, 128 -> 128, 128 -> 256 and 256 -> 256 layers (got %d -> %d)", Cin, Cout);
+  TTK_REQUIRE(((Cin == 128 && Cout == 128) || w) && (!fused_f16(Cin) || wsplit),
+              "pwconv1x1_bwd_fused: the fp16 forms (128 and more input channels; 64 -> 128 in the default mode) need the prepared weight block, all but 128 -> 128 the raw weights");
+  const int ntiles = (int)ceil_div(M, fused_f16(Cin) ? kF16BM : kFusedBM), grid = fused_grid(M, Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   if (fused_f16(Cin)) {
     // prepared block (ttk_pwconv_prepare_weights, fp16 mode): [forward planes 4n][data-gradient planes 4n][|w| maximum]
@@ -570,7 +850,11 @@ int ttk_pwconv1x1_bwd_fused(const float* g, const float* y, const float* bn_pw, 
     const unsigned char* ws = static_cast<const unsigned char*>(wsplit);
     const uint16_t* wq = reinterpret_cast<const uint16_t*>(ws + prep_bwd_offset(n));
     const float* wmx = reinterpret_cast<const float*>(ws + prep_hdr_offset(n));
-    if (Cin == 128)
+    if (fused_wide(Cin, Cout) && Cin == 128)
+      hipLaunchKernelGGL((pw_bwd_fused16w_k<128>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, w, wmx, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
+    else if (fused_wide(Cin, Cout))  // two workgroups (input-channel halves) per walker
+      hipLaunchKernelGGL((pw_bwd_fused16w_k<256>), dim3(2 * grid), dim3(512), 0, st, g, y, bn_pw, w, wmx, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
+    else if (Cin == 128)
       hipLaunchKernelGGL((pw_bwd_fused16_k<128, 128>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, wq, w, wmx, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
     else
       hipLaunchKernelGGL((pw_bwd_fused16_k<64, 128>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, wq, w, wmx, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);

@@ -486,7 +486,7 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
             if _EXP_TENSOR_HOOK is not None:
                 _EXP_TENSOR_HOOK("g", k, g_dw)
         elif fused_rows:
-            # the first three pointwise layers (HBM-bound, the largest activations): weight and data gradient in ONE kernel - g,
+            # the first five pointwise layers (32 -> 64 .. 256 -> 256: HBM-bound, the largest activations): weight and data gradient in ONE kernel - g,
             # the conv output and the depthwise output are read once instead of twice (csrc/pw_bwd_fused.hip)
             L.call("ttk_pwconv1x1_bwd_fused", p(g), p(st_pw.y), p(st_pw.bn), p(w_pw), p(ctx.prep[k]), p(st_dw.y), p(st_dw.bn), p(g_dw), p(dW),
                    p(wg_scratch), p(part), M, cin, cout)
