@@ -203,9 +203,8 @@ int ttk_dwconv3x3_bwd_data(const void* g_dw, const void* y_dw, const float* bn_d
  * Pointwise 1x1 conv = GEMM on the matrix cores - DepthWiseBlock.conv_sep, mobilenet_v1.py:67,82.
  *   y[M][Cout] = a_dw[M][Cin] . w[Cout][Cin]^T,   a_dw = max(bn_dw(ydw), 0) on load,  M = B*Ho*Wo
  * Compute-bound shapes run as split-operand products on the 16-bit matrix pipe with fp32-chain accuracy: two fp16
- * pieces per operand and three products (csrc/pwconv_f16.hip; the default), or TTK_GEMM=bf16x3: three bf16 pieces and
- * six products (csrc/pwconv_split.hip).  The HBM-bound early layers run on v_mfma_f32_32x32x2_f32 (TTK_GEMM=f32mfma:
- * every layer).  The fp16 form needs the operand bounds of row TTK_BN_AUX: bn_dw[AUX][ACT_BOUND] (forward, weight
+ * pieces per operand and three products (csrc/split16.h, csrc/pwconv_f16.hip).  The HBM-bound early layers run on
+ * v_mfma_f32_32x32x2_f32 (experiment builds, TTK_GEMM=f32mfma: every layer).  The fp16 form needs the operand bounds of row TTK_BN_AUX: bn_dw[AUX][ACT_BOUND] (forward, weight
  * gradient), bn_pw[AUX][DY_BOUND] (both gradients).
  * wsplit (forward and data gradient): scratch of ttk_pwconv_prepared_bytes(Cin, Cout) for the split weight operand,
  * or a block that ttk_pwconv_prepare_weights filled (then w / wt == NULL); NULL selects the fp32 MFMA kernels.
@@ -377,7 +376,7 @@ int ttk_bc_bn_bwd_finalize_fold(float* part, int part_rows, int C, int64_t count
  *   ttk_conv_weight_repack  w[Cout][Cin][KH][KW] -> w_fwd[.][KH*KW*Cin/32][Cout][32], w_bwd[.][KH*KW*Cout/32][Cin][32] (either may be
  *                           NULL; each a buffer of 3 * 2 bytes per weight): the 16-bit piece planes the GEMM producers
  *                           move without arithmetic - two fp16 planes of w * 2^s followed by a float header holding
- *                           max |w| (default), or TTK_GEMM=bf16x3: the three planes (h, m, l) of the exact bf16 split
+ *                           max |w|
  *   ttk_conv_fwd            y[B][Ho][Wo][Cout] raw conv output + part[ttk_partial_rows_gemm(B*Ho*Wo)][2][Cout].
  *                           a_bound: device float >= max |a_in| (the fp16 form scales by it) - the TTK_AUX_ACT_BOUND slot
  *                           of the BatchNorm block that formed a_in (ttk_bn_fwd_finalize bounds relu(bn(y)) and hence

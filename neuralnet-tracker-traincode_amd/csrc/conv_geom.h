@@ -1,4 +1,5 @@
-// Shared between pwconv_split.hip and conv.hip.
+// Shared between the pointwise-GEMM files (pwconv*.hip, pw_bwd_fused.hip) and conv.hip: operand / epilogue forms, the implicit-GEMM geometry,
+// the kernel-family switch and the layout of the prepared weight blocks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,9 +30,9 @@ struct ConvGeom {
   int par, nimg, ctile[4];
 };
 
-// TTK_GEMM=f32mfma keeps every pointwise conv on v_mfma_f32_32x32x2_f32, bf16x3 selects the 3-piece bf16 split (A/B
-// timing and numerics comparisons; the ResNet18 convolutions have no fp32 form and take bf16x3 for both)
-enum { GEMM_F16X2 = 0, GEMM_BF16X3 = 1, GEMM_F32 = 2 };
+// TTK_GEMM=f32mfma (experiment builds) keeps every pointwise conv on v_mfma_f32_32x32x2_f32 (A/B timing and numerics comparisons); the ResNet18
+// convolutions exist in the fp16 form only and refuse that mode (conv.hip)
+enum { GEMM_F16X2 = 0, GEMM_F32 = 2 };
 inline int gemm_mode() {
   static const int mode = [] {
     const char* e = exp_env("TTK_GEMM");
@@ -44,16 +45,10 @@ inline int gemm_mode() {
   return mode;
 }
 
-// Round 1's six-product bf16 split (csrc/pwconv_split.hip, TTK_GEMM=bf16x3) was removed in round 3; gemm_mode() never returns
-// GEMM_BF16X3 and these never launch.
-inline bool launch_conv_gemm(int, int, const float*, const float*, const float*, const uint16_t*, float*, const float*, const float*, float*, int64_t,
-                             int, int, const ConvGeom&, hipStream_t) { return false; }
-inline bool launch_conv_wgrad(const float*, const float*, const float*, const float*, float*, int64_t, int, int, const ConvGeom&, hipStream_t) { return false; }
-
 // Layout of a prepared weight block of n = Cin * Cout elements (ttk_pwconv_prepare_weights): [forward operand][data-gradient operand]
 // [header: |w| maximum ...].  Every reader of the block takes the offsets from here.
-inline size_t prep_bwd_offset(size_t n) { return 4 * n; }
-inline size_t prep_hdr_offset(size_t n) { return 8 * n; }
+__host__ __device__ inline size_t prep_bwd_offset(size_t n) { return 4 * n; }
+__host__ __device__ inline size_t prep_hdr_offset(size_t n) { return 8 * n; }
 
 // fp16-pipe forms (pwconv_f16.hip): Bq = two fp16 planes scaled by pow2_scale(*wmax); a_bound = bound of a plain A operand
 bool launch_conv_gemm16(int amode, int emode, const float* A0, const float* A1, const float* bnA, const float* a_bound, const uint16_t* Bq,
@@ -68,26 +63,7 @@ size_t conv_wgrad16_partial_bytes(int64_t M, int Cout, int ncols, int taps);
 __host__ __device__ inline int64_t r_plane_index(int row, int k, int rows) {
   return ((int64_t)(k >> 4) * rows + row) * 16 + ((((k >> 3) & 1) ^ ((row >> 3) & 1)) << 3) + (k & 7);
 }
-// element (row n, k) of a [rows][K] weight operand inside the fragment-ordered image of ttk_pwconv_prepare_weights (split code 3):
-// [k32 step][16-row block][plane][lane = 16 (k chunk) + row][8 k] fp16 - a wave's fragment of one block and plane is 1 KB, lane-linear
-__host__ __device__ inline int64_t x_plane_index(int row, int k, int rows, int plane) {
-  const int ks = k >> 5, q = (k >> 3) & 3, cb = row >> 4, r = row & 15;
-  return (((int64_t)ks * (rows >> 4) + cb) * 2 + plane) * 512 + (q * 16 + r) * 8 + (k & 7);
-}
 
-// Full-width GEMMs (pwconv_x.hip, round 6): they take the wide shapes in the product; the row-block kernels stay for experiment builds (TTK_GEMM_X=0)
-bool f16x_gemm_shape(int K, int Nout, int dgrad);
-int f16x_partial_rows(int64_t M, int K, int Nout, int dgrad);
-int f16x_tile_rows(int64_t M, int K, int Nout, int dgrad);
-template <int MODE>
-bool launch_f16x_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0, const float* bnE, float* part, int64_t M,
-                      int K, int Nout, void* planes, float* wmax, hipStream_t st);
-// Streaming GEMMs of the narrow HBM-bound layers (pwconv_y.hip, round 6)
-bool f16y_gemm_shape(int K, int Nout, int dgrad);
-int f16y_partial_rows(int64_t M, int K, int Nout, int dgrad);
-template <int MODE>
-bool launch_f16y_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0, const float* bnE, float* part, int64_t M,
-                      int K, int Nout, void* planes, float* wmax, hipStream_t st);
 bool f16r_gemm_shape(int K, int Nout, int dgrad);
 int f16r_partial_rows(int64_t M, int K, int Nout, int dgrad);
 int f16r_tile_rows(int64_t M, int K, int Nout, int dgrad);

@@ -20,10 +20,9 @@
 // data gradient's fragments are ds_read_b128 (4 k-values per read) - any k order is a valid contraction order.
 #include "ttk_common.h"
 #include "conv_geom.h"
+#include "split16.h"
 
 namespace ttk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kFusedBM = 64;
 
@@ -270,7 +269,7 @@ __global__ void __launch_bounds__(512) pw_bwd_fused_k(const float* __restrict__ 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The 128 -> 128 layer: the same fusion on the fp16 matrix pipe (fp32 MFMA would bind: 8.4 MFLOP per 64 rows).  Arithmetic
-// of pwconv_f16.hip: operands scaled by powers of two taken from their bounds (dy: TTK_AUX_DY_BOUND of bn_pw, a:
+// of split16.h: operands scaled by powers of two taken from their bounds (dy: TTK_AUX_DY_BOUND of bn_pw, a:
 // TTK_AUX_ACT_BOUND of bn_dw, W: the |w| maximum in the prepared block), cut into two fp16 pieces, three products.
 //
 // What makes it fit: the WEIGHTS live in registers.  Consumer wave w owns input-channel tile w (32 of 128) for both products;
@@ -283,21 +282,6 @@ __global__ void __launch_bounds__(512) pw_bwd_fused_k(const float* __restrict__ 
 // The producers load 4 rows x 4 channels per thread (as the weight-gradient kernels do) and write both layouts of dy from the
 // same registers.  Per 32 rows a consumer wave issues 24 (data gradient) + 24 (weight gradient) MFMAs = 1536 cycles against
 // 64 KB of operands through the CU (6400 cycles): memory-bound, as it should be.
-typedef _Float16 fz16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 fz16x2 __attribute__((ext_vector_type(2)));
-typedef float fz32x2 __attribute__((ext_vector_type(2)));
-typedef float fz32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int fz_swz(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 3) & 1)) << 4); }
-// h / l fp16 pieces of 4 (already scaled) values: 8 bytes each
-__device__ __forceinline__ void fz_split(fz32x4 v, uint2& h, uint2& l) {
-  const fz16x2 h01 = __builtin_convertvector(fz32x2{v.x, v.y}, fz16x2), h23 = __builtin_convertvector(fz32x2{v.z, v.w}, fz16x2);
-  const fz32x2 f01 = __builtin_convertvector(h01, fz32x2), f23 = __builtin_convertvector(h23, fz32x2);
-  const fz16x2 l01 = __builtin_convertvector(fz32x2{v.x - f01.x, v.y - f01.y}, fz16x2);
-  const fz16x2 l23 = __builtin_convertvector(fz32x2{v.z - f23.x, v.w - f23.y}, fz16x2);
-  h = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-  l = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-}
 
 constexpr int kF16BM = 32;
 template <int CIN, int COUT>
@@ -340,24 +324,24 @@ pw_bwd_fused16_k(const float* __restrict__ g, const float* __restrict__ y, const
     const bool a_on = cq < CIN / 4;
     const int cqa = a_on ? cq : 0;
     const int sub = mb >> 2, chunk = (mb >> 1) & 1, o8 = (mb & 1) * 8;
-    const fz32x4 ga = *reinterpret_cast<const fz32x4*>(bn_pw + TTK_BN_GA * COUT + 4 * cq) * sa;
-    const fz32x4 gb = *reinterpret_cast<const fz32x4*>(bn_pw + TTK_BN_GB * COUT + 4 * cq) * sa;
-    const fz32x4 gmean = *reinterpret_cast<const fz32x4*>(bn_pw + TTK_BN_GMEAN * COUT + 4 * cq);
-    const fz32x4 ymean = *reinterpret_cast<const fz32x4*>(bn_pw + TTK_BN_MEAN * COUT + 4 * cq);
-    const fz32x4 dsc = *reinterpret_cast<const fz32x4*>(bn_dw + TTK_BN_SCALE * CIN + 4 * cqa) * sx;
-    const fz32x4 dbe = *reinterpret_cast<const fz32x4*>(bn_dw + TTK_BN_BETA * CIN + 4 * cqa) * sx;
-    const fz32x4 dmean = *reinterpret_cast<const fz32x4*>(bn_dw + TTK_BN_MEAN * CIN + 4 * cqa);
-    fz32x4 rg[4], ry[4], rc[4];
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_GA * COUT + 4 * cq) * sa;
+    const f32x4 gb = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_GB * COUT + 4 * cq) * sa;
+    const f32x4 gmean = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_GMEAN * COUT + 4 * cq);
+    const f32x4 ymean = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_MEAN * COUT + 4 * cq);
+    const f32x4 dsc = *reinterpret_cast<const f32x4*>(bn_dw + TTK_BN_SCALE * CIN + 4 * cqa) * sx;
+    const f32x4 dbe = *reinterpret_cast<const f32x4*>(bn_dw + TTK_BN_BETA * CIN + 4 * cqa) * sx;
+    const f32x4 dmean = *reinterpret_cast<const f32x4*>(bn_dw + TTK_BN_MEAN * CIN + 4 * cqa);
+    f32x4 rg[4], ry[4], rc[4];
     auto load = [&](int t) {
       const int64_t r0 = (int64_t)t * BM + 4 * mb;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int64_t row = r0 + i < M ? r0 + i : M - 1;
         const float4 a = ld4nt(g + act_off(row, 4 * cq, M)), b = ld4nt(y + act_off(row, 4 * cq, M));  // activations: channel blocks (ttk_common.h)
-        rg[i] = fz32x4{a.x, a.y, a.z, a.w}; ry[i] = fz32x4{b.x, b.y, b.z, b.w};
+        rg[i] = f32x4{a.x, a.y, a.z, a.w}; ry[i] = f32x4{b.x, b.y, b.z, b.w};
         if (a_on) {
           const float4 c = ld4(ydw + act_off(row, 4 * cqa, M));
-          rc[i] = fz32x4{c.x, c.y, c.z, c.w};
+          rc[i] = f32x4{c.x, c.y, c.z, c.w};
         }
       }
     };
@@ -368,37 +352,37 @@ pw_bwd_fused16_k(const float* __restrict__ g, const float* __restrict__ y, const
       unsigned char* AT = DyT + 2 * 2 * kTY;
       float* Yc = reinterpret_cast<float*>(AT + 2 * 2 * kTA);
       const int64_t r0 = (int64_t)t * BM + 4 * mb;
-      fz32x4 dy[4], av[4];
+      f32x4 dy[4], av[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         dy[i] = ga * (rg[i] - gmean) + gb * (ry[i] - ymean);
-        if (r0 + i >= M) dy[i] = fz32x4{0.f, 0.f, 0.f, 0.f};  // rows past the end contribute nothing
+        if (r0 + i >= M) dy[i] = f32x4{0.f, 0.f, 0.f, 0.f};  // rows past the end contribute nothing
         // dy row-major: 8-byte piece cq of row 4 mb + i, 16-byte chunk XOR (row & 15)
         uint2 ph, pl;
-        fz_split(dy[i], ph, pl);
+        split16x4(dy[i], ph, pl);
         const int row = 4 * mb + i, off = row * (COUT * 2) + ((((cq >> 1) ^ (row & 15))) << 4) + (cq & 1) * 8;
         *reinterpret_cast<uint2*>(DyR + off) = ph;
         *reinterpret_cast<uint2*>(DyR + kRowPlane + off) = pl;
         if (a_on) {
-          const fz32x4 yc = rc[i] - dmean;
-          fz32x4 a = dsc * yc + dbe;
+          const f32x4 yc = rc[i] - dmean;
+          f32x4 a = dsc * yc + dbe;
           a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
-          if (r0 + i >= M) a = fz32x4{0.f, 0.f, 0.f, 0.f};
+          if (r0 + i >= M) a = f32x4{0.f, 0.f, 0.f, 0.f};
           av[i] = a;
-          *reinterpret_cast<fz32x4*>(Yc + (4 * mb + i) * kLdc + 4 * cqa) = yc;
+          *reinterpret_cast<f32x4*>(Yc + (4 * mb + i) * kLdc + 4 * cqa) = yc;
         }
       }
       // transposed: channel 4 cq + e, four consecutive rows 4 mb .. 4 mb + 3 (k) -> 8 bytes per plane
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         uint2 ph, pl;
-        fz_split(fz32x4{dy[0][e], dy[1][e], dy[2][e], dy[3][e]}, ph, pl);
-        const int offy = sub * (2 * kTY) + fz_swz(4 * cq + e, chunk) + o8;
+        split16x4(f32x4{dy[0][e], dy[1][e], dy[2][e], dy[3][e]}, ph, pl);
+        const int offy = sub * (2 * kTY) + swz16(4 * cq + e, chunk) + o8;
         *reinterpret_cast<uint2*>(DyT + offy) = ph;
         *reinterpret_cast<uint2*>(DyT + kTY + offy) = pl;
         if (a_on) {
-          fz_split(fz32x4{av[0][e], av[1][e], av[2][e], av[3][e]}, ph, pl);
-          const int offa = sub * (2 * kTA) + fz_swz(4 * cqa + e, chunk) + o8;
+          split16x4(f32x4{av[0][e], av[1][e], av[2][e], av[3][e]}, ph, pl);
+          const int offa = sub * (2 * kTA) + swz16(4 * cqa + e, chunk) + o8;
           *reinterpret_cast<uint2*>(AT + offa) = ph;
           *reinterpret_cast<uint2*>(AT + kTA + offa) = pl;
         }
@@ -424,14 +408,14 @@ pw_bwd_fused16_k(const float* __restrict__ g, const float* __restrict__ y, const
     const int cit = wave % NCI, cog = wave / NCI;   // weight gradient: ci tile, group of co tiles
     const int ci_dg = 32 * (has_dg ? wave : 0) + r32, ci_wg = 32 * cit + r32;
     // data-gradient B fragments: W^T planes [co / 32][ci][32] of the prepared operand, k16 step s, lane half h: co 16 s + 8 h ..
-    fz16x8 Wf[COUT / 16][2];
+    f16x8 Wf[COUT / 16][2];
 #pragma unroll
     for (int s = 0; s < COUT / 16; ++s) {
       const int co = 16 * s + 8 * h;
       if (CIN == 128) {
         const size_t idx = ((size_t)(co >> 5) * CIN + ci_dg) * 32 + (co & 31);
-        Wf[s][0] = *reinterpret_cast<const fz16x8*>(wq + idx);
-        Wf[s][1] = *reinterpret_cast<const fz16x8*>(wq + (size_t)CIN * COUT + idx);
+        Wf[s][0] = *reinterpret_cast<const f16x8*>(wq + idx);
+        Wf[s][1] = *reinterpret_cast<const f16x8*>(wq + (size_t)CIN * COUT + idx);
       } else {
         // 64 -> 128: the prepared block of this layer holds no fp16 data-gradient planes (its stand-alone data gradient runs on
         // fp32 MFMA) - cut the raw weights here, once per workgroup, with the block's |w| scale
@@ -469,26 +453,26 @@ pw_bwd_fused16_k(const float* __restrict__ g, const float* __restrict__ y, const
 #pragma unroll
         for (int s = 0; s < COUT / 16; ++s) {
           const int off = r32 * (COUT * 2) + ((((2 * s + h) ^ (r32 & 15))) << 4);
-          const fz16x8 ah = *reinterpret_cast<const fz16x8*>(DyR + off), al = *reinterpret_cast<const fz16x8*>(DyR + kRowPlane + off);
+          const f16x8 ah = *reinterpret_cast<const f16x8*>(DyR + off), al = *reinterpret_cast<const f16x8*>(DyR + kRowPlane + off);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, Wf[s][1], acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, Wf[s][0], acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, Wf[s][0], acc, 0, 0, 0);
         }
       }
       // ---- weight gradient: dW[co tile][this wave's ci tile] += dy^T a over the 32 rows (two k16 stages)
-      fz16x8 bh[2], bl[2];
+      f16x8 bh[2], bl[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const int off = s * (2 * kTA) + fz_swz(ci_wg, h);
-        bh[s] = *reinterpret_cast<const fz16x8*>(AT + off);
-        bl[s] = *reinterpret_cast<const fz16x8*>(AT + kTA + off);
+        const int off = s * (2 * kTA) + swz16(ci_wg, h);
+        bh[s] = *reinterpret_cast<const f16x8*>(AT + off);
+        bl[s] = *reinterpret_cast<const f16x8*>(AT + kTA + off);
       }
 #pragma unroll
       for (int tt = 0; tt < COW; ++tt)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const int off = s * (2 * kTY) + fz_swz(32 * (cog * COW + tt) + r32, h);
-          const fz16x8 ah = *reinterpret_cast<const fz16x8*>(DyT + off), al = *reinterpret_cast<const fz16x8*>(DyT + kTY + off);
+          const int off = s * (2 * kTY) + swz16(32 * (cog * COW + tt) + r32, h);
+          const f16x8 ah = *reinterpret_cast<const f16x8*>(DyT + off), al = *reinterpret_cast<const f16x8*>(DyT + kTY + off);
           wacc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[s], wacc[tt], 0, 0, 0);
           wacc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[s], wacc[tt], 0, 0, 0);
           wacc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[s], wacc[tt], 0, 0, 0);
@@ -544,8 +528,6 @@ pw_bwd_fused16_k(const float* __restrict__ g, const float* __restrict__ y, const
 //    epilogue: a stage is 32 + 16 + 16.5 KB, double-buffered.
 // A thread loads 4 rows x 4 output channels of g and y (threads 0 .. 255 also 4 x 4 of ydw) one tile ahead of the tile it
 // stores to LDS, two ahead of the tile the workgroup multiplies: the loads stay in flight under the MFMAs of a whole stage.
-typedef short fzs16x4 __attribute__((ext_vector_type(4)));
-typedef short fzs16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kWideCW = 128;  // input channels per workgroup
 struct WideShape {
@@ -562,13 +544,13 @@ template <typename T> __device__ __forceinline__ T* wide_at(T* p, unsigned byte_
 }
 __device__ __forceinline__ int wide_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
-__device__ __forceinline__ fz16x8 wide_tr_frag(const unsigned char* p0, const unsigned char* p1) {
+__device__ __forceinline__ f16x8 wide_tr_frag(const unsigned char* p0, const unsigned char* p1) {
   // rows 8 g .. 8 g + 3 and 8 g + 4 .. 8 g + 7 of a 16-channel block (the lane's addresses hold its row q and channel quad p):
   // element j = the lane's channel at row 8 g + j
-  const fzs16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fzs16x4*)(p0));
-  const fzs16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fzs16x4*)(p1));
-  const fzs16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(fz16x8, v);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p0));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p1));
+  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(f16x8, v);
 }
 
 // CINT = 128: workgroup b walks the row tiles b, b + grid, ..  CINT = 256: `walkers` = grid / 2 pairs of workgroups; the two
@@ -622,7 +604,7 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
   // ---- staging role: g and y: rows 4 mb .. 4 mb + 3, output channels 4 cq .. 4 cq + 3; ydw: rows 2 rp, 2 rp + 1, input channels
   // cio + 4 cqa .. (a wave covers whole 128-byte rows of one channel block).  Offsets are 32-bit: the launch holds M * 256 below 2^30.
   const unsigned Mu = (unsigned)M;
-  fz32x4 rg[4], ry[4], rc[2];
+  f32x4 rg[4], ry[4], rc[2];
   auto load = [&](int t) {
     const int ft = fresh_tid(), mb = ft & 7, cq = ft >> 3, rp = (wave & 1) * 8 + ((ft & 63) >> 3), cqa = (wave >> 1) * 8 + (ft & 7);
     const unsigned r0 = (unsigned)t * BM + 4 * mb, q0 = (unsigned)t * BM + 2 * rp;
@@ -631,13 +613,13 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
       const unsigned row = r0 + i < Mu ? r0 + i : Mu - 1;
       const unsigned off = (((cq >> 3) * Mu + row) * kCB + 4 * (cq & 7)) * 4;  // activations: channel blocks (ttk_common.h)
       const float4 a = ld4nt(wide_at(g, off)), b = ld4nt(wide_at(y, off));
-      rg[i] = fz32x4{a.x, a.y, a.z, a.w}; ry[i] = fz32x4{b.x, b.y, b.z, b.w};
+      rg[i] = f32x4{a.x, a.y, a.z, a.w}; ry[i] = f32x4{b.x, b.y, b.z, b.w};
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const unsigned row = q0 + i < Mu ? q0 + i : Mu - 1;
       const float4 c = ld4(wide_at(ydw, ((((cio >> 5) + (cqa >> 3)) * Mu + row) * kCB + 4 * (cqa & 7)) * 4));  // (read again by the depthwise backward: cached)
-      rc[i] = fz32x4{c.x, c.y, c.z, c.w};
+      rc[i] = f32x4{c.x, c.y, c.z, c.w};
     }
   };
   auto store = [&](int t, int st) {
@@ -649,38 +631,37 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
     float* Yc = reinterpret_cast<float*>(AT + 2 * kAP);
     const unsigned r0 = (unsigned)t * BM + 4 * mb, q0 = (unsigned)t * BM + 2 * rp;
     {
-      const fz32x4 dsc = *reinterpret_cast<const fz32x4*>(cdw + 4 * cqa), dbe = *reinterpret_cast<const fz32x4*>(cdw + CW + 4 * cqa);
-      const fz32x4 dmean = *reinterpret_cast<const fz32x4*>(cdw + 2 * CW + 4 * cqa);
-      fz32x4 av[2];
+      const f32x4 dsc = *reinterpret_cast<const f32x4*>(cdw + 4 * cqa), dbe = *reinterpret_cast<const f32x4*>(cdw + CW + 4 * cqa);
+      const f32x4 dmean = *reinterpret_cast<const f32x4*>(cdw + 2 * CW + 4 * cqa);
+      f32x4 av[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const fz32x4 yc = rc[i] - dmean;
-        fz32x4 a = dsc * yc + dbe;
+        const f32x4 yc = rc[i] - dmean;
+        f32x4 a = dsc * yc + dbe;
         a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
-        if (q0 + i >= Mu) a = fz32x4{0.f, 0.f, 0.f, 0.f};  // rows past the end contribute nothing
+        if (q0 + i >= Mu) a = f32x4{0.f, 0.f, 0.f, 0.f};  // rows past the end contribute nothing
         av[i] = a;
-        *reinterpret_cast<fz32x4*>(Yc + (2 * rp + i) * kLdc + 4 * cqa) = yc;
+        *reinterpret_cast<f32x4*>(Yc + (2 * rp + i) * kLdc + 4 * cqa) = yc;
       }
       // transposed: channel 4 cqa + e, rows 2 rp, 2 rp + 1 (k) -> 4 bytes per plane
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const fz32x2 v{av[0][e], av[1][e]};
-        const fz16x2 vh = __builtin_convertvector(v, fz16x2);
-        const fz16x2 vl = __builtin_convertvector(v - __builtin_convertvector(vh, fz32x2), fz16x2);
+        unsigned vh, vl;
+        split16x2(av[0][e], av[1][e], vh, vl);
         const int offa = (4 * cqa + e) * 64 + ((((rp >> 2) ^ (cqa & 3))) << 4) + (rp & 3) * 4;
-        *reinterpret_cast<unsigned*>(AT + offa) = __builtin_bit_cast(unsigned, vh);
-        *reinterpret_cast<unsigned*>(AT + kAP + offa) = __builtin_bit_cast(unsigned, vl);
+        *reinterpret_cast<unsigned*>(AT + offa) = vh;
+        *reinterpret_cast<unsigned*>(AT + kAP + offa) = vl;
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    const fz32x4 ga = *reinterpret_cast<const fz32x4*>(cpw + 4 * cq), gb = *reinterpret_cast<const fz32x4*>(cpw + COUT + 4 * cq);
-    const fz32x4 gmean = *reinterpret_cast<const fz32x4*>(cpw + 2 * COUT + 4 * cq), ymean = *reinterpret_cast<const fz32x4*>(cpw + 3 * COUT + 4 * cq);
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(cpw + 4 * cq), gb = *reinterpret_cast<const f32x4*>(cpw + COUT + 4 * cq);
+    const f32x4 gmean = *reinterpret_cast<const f32x4*>(cpw + 2 * COUT + 4 * cq), ymean = *reinterpret_cast<const f32x4*>(cpw + 3 * COUT + 4 * cq);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      fz32x4 dy = ga * (rg[i] - gmean) + gb * (ry[i] - ymean);
-      if (r0 + i >= Mu) dy = fz32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 dy = ga * (rg[i] - gmean) + gb * (ry[i] - ymean);
+      if (r0 + i >= Mu) dy = f32x4{0.f, 0.f, 0.f, 0.f};
       uint2 ph, pl;
-      fz_split(dy, ph, pl);
+      split16x4(dy, ph, pl);
       // row 4 mb + i: wide_swz(row) = (i << 2) | (mb & 3)
       const int off = (dyoff ^ (i << 6)) + i * 256;
       *reinterpret_cast<uint2*>(DyR + off) = ph;
@@ -691,7 +672,7 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
 
   // ---- multiplying role: input channel ci (of the workgroup's 128) on the lane, lane group grp = k octet / row quad
   const int cil = 16 * wave + n16, ci = cio + cil;
-  fz16x8 Wf[COUT / 32][2];  // B fragments of the data gradient: W^T, k32 step s: co 32 s + 8 grp + j
+  f16x8 Wf[COUT / 32][2];  // B fragments of the data gradient: W^T, k32 step s: co 32 s + 8 grp + j
 #pragma unroll
   for (int s = 0; s < COUT / 32; ++s)
 #pragma unroll
@@ -702,9 +683,9 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
       Wf[s][1][e] = (_Float16)(xs - (float)hh);
     }
   const float inv_dg = uni(1.f / (sa * sw)), inv_wg = uni(1.f / (sa * sx));
-  fz32x4 wacc[COUT / 16];
+  f32x4 wacc[COUT / 16];
 #pragma unroll
-  for (int ct = 0; ct < COUT / 16; ++ct) wacc[ct] = fz32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ct = 0; ct < COUT / 16; ++ct) wacc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   // (the BatchNorm-backward sums of the epilogue are kept per lane in LDS, the ReLU constants read from cdw - their power-of-two scale
   // leaves the sign alone: six registers that the kernel does not have)
   acc12[tid] = 0.f; acc12[512 + tid] = 0.f;
@@ -723,23 +704,23 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
     const float* Yc = reinterpret_cast<const float*>(AT + 2 * kAP);
     const unsigned m0 = (unsigned)t * BM;
     // ---- data gradient: 32 rows x this wave's 16 ci, contraction over the 256 co
-    fz32x4 acc[2] = {fz32x4{0.f, 0.f, 0.f, 0.f}, fz32x4{0.f, 0.f, 0.f, 0.f}};
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int s = 0; s < COUT / 32; ++s)
 #pragma unroll
       for (int rt = 0; rt < 2; ++rt) {
         const int off = (rbase ^ (64 * (s & 3))) + (s >> 2) * (kDyP / 2) + rt * 16 * 256;
-        const fz16x8 ah = *reinterpret_cast<const fz16x8*>(DyR + off), al = *reinterpret_cast<const fz16x8*>(DyR + kDyP + off);
+        const f16x8 ah = *reinterpret_cast<const f16x8*>(DyR + off), al = *reinterpret_cast<const f16x8*>(DyR + kDyP + off);
         acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, Wf[s][1], acc[rt], 0, 0, 0);
         acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, Wf[s][0], acc[rt], 0, 0, 0);
         acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, Wf[s][0], acc[rt], 0, 0, 0);
       }
     // ---- weight gradient: dW[co block ct][this wave's 16 ci] += dy^T a over the 32 rows (one k32 step)
-    const fz16x8 bh = *reinterpret_cast<const fz16x8*>(AT + aoff), bl = *reinterpret_cast<const fz16x8*>(AT + kAP + aoff);
+    const f16x8 bh = *reinterpret_cast<const f16x8*>(AT + aoff), bl = *reinterpret_cast<const f16x8*>(AT + kAP + aoff);
 #pragma unroll
     for (int ct = 0; ct < COUT / 16; ++ct) {
       const int o0 = (tb0 ^ (32 * (ct & 7))) + (ct >> 3) * (kDyP / 2), o1 = (tb0 ^ (32 * (ct & 7) ^ 16)) + (ct >> 3) * (kDyP / 2) + 4 * 256;
-      const fz16x8 ah = wide_tr_frag(DyR + o0, DyR + o1), al = wide_tr_frag(DyR + kDyP + o0, DyR + kDyP + o1);
+      const f16x8 ah = wide_tr_frag(DyR + o0, DyR + o1), al = wide_tr_frag(DyR + kDyP + o0, DyR + kDyP + o1);
       wacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, wacc[ct], 0, 0, 0);
       wacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, wacc[ct], 0, 0, 0);
       wacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, wacc[ct], 0, 0, 0);

@@ -16,13 +16,11 @@
 // one 32x32x2 MFMA - the sum over k is order-free, so no shuffling is needed.
 #include "ttk_common.h"
 #include "conv_geom.h"
-#include <type_traits>
+#include "split16.h"
 #include <stdlib.h>
 #include <string.h>
 
 namespace ttk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = TTK_GEMM_BLOCK_M;  // 128 rows of M per workgroup
 constexpr int BKT = 32;               // contraction slice per LDS stage
@@ -392,33 +390,16 @@ bool launch_f16t_wgrad(const TG* g, const T* y, const float* bn_pw, const T* ydw
                        int Cin, int Cout, hipStream_t st);
 size_t f16t_wgrad_scratch_bytes(int64_t M, int Cin, int Cout);
 
-// (round 1's bf16 x 3 split kernels were removed in round 3: gemm_mode() never returns GEMM_BF16X3, these never launch)
-template <int MODE>
-inline bool launch_split_gemm(const float*, const float*, const float*, const float*, float*, const float*, const float*, float*, int64_t, int, int, void*,
-                              hipStream_t) { return false; }
-inline bool split_gemm_shape(int, int) { return false; }
-inline bool launch_split_wgrad(const float*, const float*, const float*, const float*, const float*, float*, int64_t, int, int, hipStream_t) { return false; }
-
-// Layout of a prepared weight block of n = Cin*Cout elements.  fp16 / fp32 modes: [forward operand 4n][data-gradient
-// operand 4n][header: |w| maximum] - an operand is two fp16 planes or, for the shapes that stay on the fp32 kernels,
-// the fp32 rows; bf16 mode: [forward 6n][data gradient 6n].
+// Layout of a prepared weight block of n = Cin*Cout elements: [forward operand 4n][data-gradient operand 4n][header: |w| maximum] -
+// an operand is two fp16 planes or, for the shapes that stay on the fp32 kernels, the fp32 rows.
 // (prep_bwd_offset / prep_hdr_offset: conv_geom.h - shared with the fused backward kernels of pw_bwd_fused.hip)
 
 template <int MODE, typename T, typename TO>
-static bool launch_gemm(const TO* A0, const T* A1, const float* bnA, const float* Bm, TO* out, const T* E0,
+static void launch_gemm(const TO* A0, const T* A1, const float* bnA, const float* Bm, TO* out, const T* E0,
                         const float* bnE, float* part, int64_t M, int K, int Nout, void* region, float* hdr, hipStream_t st) {
   const int mode = gemm_mode();
-  if constexpr (std::is_same<T, float>::value && std::is_same<TO, float>::value) {
-    if (mode == GEMM_F16X2 && launch_f16y_gemm<MODE == MODE_FWD ? 0 : 1>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return true;
-    if (mode == GEMM_F16X2 && launch_f16x_gemm<MODE == MODE_FWD ? 0 : 1>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return true;
-  }
-  if (mode == GEMM_F16X2 && launch_f16r_gemm<MODE, T, TO>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return true;
-  if (mode == GEMM_F16X2 && launch_f16_gemm<MODE, T, TO>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return true;
-  if constexpr (!Act<T>::kBf16 && !Act<TO>::kBf16) {
-    if (mode == GEMM_BF16X3 && launch_split_gemm<MODE>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, st)) return true;
-  } else {
-    if (mode == GEMM_BF16X3) return false;  // the 3-piece bf16 kernels read fp32 activations only
-  }
+  if (mode == GEMM_F16X2 && launch_f16r_gemm<MODE, T, TO>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return;
+  if (mode == GEMM_F16X2 && launch_f16_gemm<MODE, T, TO>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return;
   if (!Bm) Bm = static_cast<const float*>(region);  // prepared operand of a shape that stays on the fp32 kernels
   const dim3 blk(kBlock);
   const unsigned gm = (unsigned)ceil_div(M, BM);
@@ -431,7 +412,6 @@ static bool launch_gemm(const TO* A0, const T* A1, const float* bnA, const float
     hipLaunchKernelGGL((pw_gemm_k<64, 2, 2, MODE, 2, T, TO>), dim3(gm), blk, 0, st, A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout);
   else
     hipLaunchKernelGGL((pw_gemm_k<32, 4, 1, MODE, 2, T, TO>), dim3(gm), blk, 0, st, A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout);
-  return true;
 }
 
 // ---- all pointwise layers' weight operands (ttk_pwconv_prepare_weights) -----------------------------------------------
@@ -445,37 +425,20 @@ struct PrepArgs {
   int n, mode;
 };
 
-// element (row, k) of a [rows][K] operand: fp32 in place, or its piece planes in the split kernels' [K/32][rows][32] order
-// (bf16 mode: three exact pieces; fp16 mode: two round-to-nearest pieces of x * s)
-__device__ __forceinline__ void prep_store(unsigned char* region, int split, int mode, float s, int row, int k, int rows, int K, float x) {
+// element (row, k) of a [rows][K] operand: fp32 in place (split 0), or the two fp16 pieces of x * s (split16.h) in the planes of the
+// split kernels: [K/32][rows][32] (split 1) or the row-block kernels' [K/16][rows][16] (split 2)
+__device__ __forceinline__ void prep_store(unsigned char* region, int split, float s, int row, int k, int rows, int K, float x) {
   const int64_t n = (int64_t)rows * K;
   if (!split) {
     reinterpret_cast<float*>(region)[(int64_t)row * K + k] = x;
     return;
   }
   uint16_t* q = reinterpret_cast<uint16_t*>(region);
-  if (split == 3) {  // fragment-ordered image, the two planes of a block side by side
-    const float xs = x * s;
-    const _Float16 hh = (_Float16)xs;
-    const _Float16 ll = (_Float16)(xs - (float)hh);
-    q[x_plane_index(row, k, rows, 0)] = __builtin_bit_cast(uint16_t, hh);
-    q[x_plane_index(row, k, rows, 1)] = __builtin_bit_cast(uint16_t, ll);
-    return;
-  }
   const int64_t idx = split == 2 ? r_plane_index(row, k, rows) : ((int64_t)(k >> 5) * rows + row) * 32 + (k & 31);
-  if (mode == GEMM_BF16X3) {
-    const float r1 = x - __uint_as_float(__float_as_uint(x) & 0xffff0000u);
-    const float r2 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
-    q[idx] = (uint16_t)(__float_as_uint(x) >> 16);
-    q[n + idx] = (uint16_t)(__float_as_uint(r1) >> 16);
-    q[2 * n + idx] = (uint16_t)(__float_as_uint(r2) >> 16);
-  } else {
-    const float xs = x * s;
-    const _Float16 hh = (_Float16)xs;
-    const _Float16 ll = (_Float16)(xs - (float)hh);
-    q[idx] = __builtin_bit_cast(uint16_t, hh);
-    q[n + idx] = __builtin_bit_cast(uint16_t, ll);
-  }
+  uint16_t h, l;
+  split16(x * s, h, l);
+  q[idx] = h;
+  q[n + idx] = l;
 }
 
 __device__ __forceinline__ int prep_layer(const PrepArgs& a) {
@@ -517,7 +480,7 @@ __global__ void __launch_bounds__(kBlock) pw_prepare_weights_k(PrepArgs a) {
   const int64_t n = (int64_t)Cin * Cout;
   const float* w = a.w[l];
   unsigned char* fwd = a.out[l];
-  unsigned char* bwd = a.out[l] + (a.mode == GEMM_BF16X3 ? 6 : 4) * n;
+  unsigned char* bwd = a.out[l] + prep_bwd_offset(n);
   float s = 1.f;
   if (a.mode == GEMM_F16X2) {
     static_assert(kPrepParts == kWave, "one value per lane");
@@ -531,10 +494,10 @@ __global__ void __launch_bounds__(kBlock) pw_prepare_weights_k(PrepArgs a) {
   for (int i = ty; i < 32; i += kBlock / 32) {
     const float x = w[(int64_t)(r0 + i) * Cin + c0 + tx];
     t[i][tx] = x;
-    prep_store(fwd, a.split_fwd[l], a.mode, s, r0 + i, c0 + tx, Cout, Cin, x);
+    prep_store(fwd, a.split_fwd[l], s, r0 + i, c0 + tx, Cout, Cin, x);
   }
   __syncthreads();
-  for (int i = ty; i < 32; i += kBlock / 32) prep_store(bwd, a.split_bwd[l], a.mode, s, c0 + i, r0 + tx, Cin, Cout, t[tx][i]);
+  for (int i = ty; i < 32; i += kBlock / 32) prep_store(bwd, a.split_bwd[l], s, c0 + i, r0 + tx, Cin, Cout, t[tx][i]);
 }
 
 }  // namespace ttk
@@ -544,16 +507,11 @@ using namespace ttk;
 extern "C" {
 
 int ttk_partial_rows_pwconv(int64_t M, int K, int Nout, int dgrad) {
-  const int yrows = f16y_partial_rows(M, K, Nout, dgrad);
-  if (yrows) return yrows;
-  const int x = f16x_partial_rows(M, K, Nout, dgrad);
-  if (x) return x;
   const int r = f16r_partial_rows(M, K, Nout, dgrad);
   return r ? r : (int)ceil_div(M, BM);
 }
 int ttk_pwconv_tile_rows(int64_t M, int K, int Nout, int dgrad) {
-  const int x = f16x_tile_rows(M, K, Nout, dgrad);
-  return x ? x : f16r_tile_rows(M, K, Nout, dgrad);
+  return f16r_tile_rows(M, K, Nout, dgrad);
 }
 
 int ttk_pwconv1x1_fwd(const void* ydw, const float* bn_dw, const float* w, void* y, float* part, const float* pivot, int64_t M, int Cin,
@@ -564,10 +522,8 @@ int ttk_pwconv1x1_fwd(const void* ydw, const float* bn_dw, const float* w, void*
   unsigned char* ws = static_cast<unsigned char*>(wsplit);
   const size_t n = (size_t)Cin * Cout;
   float* hdr = ws ? reinterpret_cast<float*>(ws + prep_hdr_offset(n)) : nullptr;
-  bool ok = false;
-  TTK_ACT_DISPATCH(act_bf16, ok = launch_gemm<MODE_FWD, ActT, ActT>((const ActT*)ydw, nullptr, bn_dw, w, (ActT*)y, nullptr, pivot, part, M, Cin, Cout, ws,
-                                                              hdr, (hipStream_t)stream));
-  TTK_REQUIRE(ok, "pwconv1x1_fwd: bf16 activations need TTK_GEMM=f16x2 (default) or f32mfma");
+  TTK_ACT_DISPATCH(act_bf16, launch_gemm<MODE_FWD, ActT, ActT>((const ActT*)ydw, nullptr, bn_dw, w, (ActT*)y, nullptr, pivot, part, M, Cin, Cout, ws,
+                                                         hdr, (hipStream_t)stream));
   TTK_LAUNCH_CHECK("pwconv1x1_fwd");
 }
 
@@ -582,10 +538,8 @@ int ttk_pwconv1x1_bwd_data(const void* g, const void* y, const float* bn_pw, con
   unsigned char* region = (ws && !wt) ? ws + prep_bwd_offset(n) : ws;  // data-gradient half of a prepared block
   float* hdr = ws ? reinterpret_cast<float*>(ws + prep_hdr_offset(n)) : nullptr;
   // contraction over Cout, output columns = Cin, B operand = wt[Cin][Cout]
-  bool ok = false;
-  TTK_ACT_DISPATCH(act_bf16, ok = launch_gemm<MODE_DGRAD, ActT, GradT>((const GradT*)g, (const ActT*)y, bn_pw, wt, (GradT*)g_dw, (const ActT*)ydw, bn_dw, part,
-                                                                M, Cout, Cin, region, hdr, (hipStream_t)stream));
-  TTK_REQUIRE(ok, "pwconv1x1_bwd_data: bf16 activations need TTK_GEMM=f16x2 (default) or f32mfma");
+  TTK_ACT_DISPATCH(act_bf16, launch_gemm<MODE_DGRAD, ActT, GradT>((const GradT*)g, (const ActT*)y, bn_pw, wt, (GradT*)g_dw, (const ActT*)ydw, bn_dw, part,
+                                                           M, Cout, Cin, region, hdr, (hipStream_t)stream));
   TTK_LAUNCH_CHECK("pwconv1x1_bwd_data");
 }
 
@@ -614,8 +568,6 @@ size_t ttk_pwconv_wgrad_partial_bytes(int64_t M, int Cin, int Cout) {
     if (t) return t;
     const size_t b = f16_wgrad_partial_bytes(M, Cin, Cout);
     if (b) return b;
-  } else if (gemm_mode() == GEMM_BF16X3 && Cin >= 128 && Cout >= 128 && (int64_t)Cin * Cout >= 128 * 256) {
-    return 0;  // the bf16 kernels have no deterministic form
   }
   int bn, bk, tiles;
   int64_t slices, rows;
@@ -627,7 +579,6 @@ int ttk_pwconv1x1_bwd_weight(const void* g, const void* y, const float* bn_pw, c
                              float* partial, int64_t M, int Cin, int Cout, int act_bf16, ttk_stream_t stream) {
   TTK_REQUIRE(g && y && bn_pw && ydw && bn_dw && dw, "pwconv1x1_bwd_weight: null pointer");
   TTK_REQUIRE(pw_shape_ok(M, Cin, Cout), "pwconv1x1_bwd_weight: unsupported shape");
-  TTK_REQUIRE(!(act_bf16 && gemm_mode() == GEMM_BF16X3), "pwconv1x1_bwd_weight: bf16 activations need TTK_GEMM=f16x2 (default) or f32mfma");
   if (gemm_mode() == GEMM_F16X2) {
     bool done = false;
     TTK_ACT_DISPATCH(act_bf16, done = launch_f16t_wgrad<ActT, GradT>((const GradT*)g, (const ActT*)y, bn_pw, (const ActT*)ydw, bn_dw, dw, partial, M, Cin, Cout,
@@ -636,10 +587,6 @@ int ttk_pwconv1x1_bwd_weight(const void* g, const void* y, const float* bn_pw, c
     TTK_ACT_DISPATCH(act_bf16, done = launch_f16_wgrad<ActT, GradT>((const GradT*)g, (const ActT*)y, bn_pw, (const ActT*)ydw, bn_dw, dw, partial, M, Cin, Cout,
                                                              (hipStream_t)stream));
     if (done) { TTK_LAUNCH_CHECK("pwconv1x1_bwd_weight"); }
-  }
-  if (gemm_mode() == GEMM_BF16X3 && launch_split_wgrad((const float*)g, (const float*)y, bn_pw, (const float*)ydw, bn_dw, dw, M, Cin, Cout,
-                                                      (hipStream_t)stream)) {
-    TTK_LAUNCH_CHECK("pwconv1x1_bwd_weight");
   }
   int bn, bk, tiles;
   int64_t slices, rows;
@@ -689,10 +636,9 @@ int ttk_pwconv_prepare_weights(int n, const float* const* w, const int* cin, con
     a.cout[i] = cout[i];
     a.first_tile[i] = tiles;
     tiles += (cin[i] / 32) * (cout[i] / 32);
-    // 0: fp32 rows; 1: piece planes [K/32][rows][32]; 2: the row-block kernels' planes [K/16][rows][16] (pwconv_r.hip); 3: the full-width kernels'
-    // fragment-ordered image (pwconv_x.hip)
-    a.split_fwd[i] = a.mode == GEMM_F16X2 ? ((f16y_gemm_shape(cin[i], cout[i], 0) || f16x_gemm_shape(cin[i], cout[i], 0)) ? 3 : f16r_gemm_shape(cin[i], cout[i], 0) ? 2 : f16_gemm_shape(cin[i], cout[i])) : (a.mode == GEMM_BF16X3 && split_gemm_shape(cin[i], cout[i]));
-    a.split_bwd[i] = a.mode == GEMM_F16X2 ? ((f16y_gemm_shape(cout[i], cin[i], 1) || f16x_gemm_shape(cout[i], cin[i], 1)) ? 3 : f16r_gemm_shape(cout[i], cin[i], 1) ? 2 : f16_gemm_shape(cout[i], cin[i])) : (a.mode == GEMM_BF16X3 && split_gemm_shape(cout[i], cin[i]));
+    // 0: fp32 rows; 1: piece planes [K/32][rows][32]; 2: the row-block kernels' planes [K/16][rows][16] (pwconv_r.hip)
+    a.split_fwd[i] = a.mode != GEMM_F16X2 ? 0 : f16r_gemm_shape(cin[i], cout[i], 0) ? 2 : f16_gemm_shape(cin[i], cout[i]);
+    a.split_bwd[i] = a.mode != GEMM_F16X2 ? 0 : f16r_gemm_shape(cout[i], cin[i], 1) ? 2 : f16_gemm_shape(cout[i], cin[i]);
   }
   a.first_tile[n] = tiles;
   hipStream_t st = (hipStream_t)stream;

@@ -1,37 +1,17 @@
 // Pointwise 1x1 convolutions of the compute-bound layers as fp32 GEMMs on the fp16 matrix pipe with a 2-piece
 // round-to-nearest operand split.  Reference: DepthWiseBlock.conv_sep + bn_sep, backbones/mobilenet_v1.py:67-68,82-84.
 //
-// Arithmetic.  Every fp32 operand value x of a tensor with a known magnitude bound is scaled by a power of two S (exact)
-// so that |x S| < 2^15 and cut into two fp16 pieces,
-//     h = fp16(x S)  (round to nearest, 11 significant bits),   l = fp16(x S - h)   (the next 11 bits; x S - h is exact),
-// so x S = h + l up to 2^-23 |x S|.  A product a*b is accumulated in fp32 as  h_a l_b + l_a h_b + h_a h_b  (three
-// v_mfma_f32_32x32x16_f16, each piece product exact in fp32; the dropped l_a l_b is below 2^-24 |a b|) and the tile is
-// multiplied by 1/(S_a S_b) on its way out.  Measured against an fp64 product this is as close as a chain of fp32 fmas
-// (tests/test_pwconv_gpu.py holds every shape to that criterion; tools/exp/split16.py is the numpy model) - the same
-// accuracy class as the 3-piece bf16 split of pwconv_split.hip (six products) at HALF the matrix work, two thirds of
-// the LDS and L2 bytes and a cheaper conversion (v_cvt_pk_f16_f32 instead of mask/subtract chains).
+// Arithmetic, operand scales and range: split16.h.
 //
-// Range.  fp16 has 5 exponent bits: pieces below 2^-14 lose bits and anything above 65504 overflows, so each operand
-// tensor carries an upper bound of its magnitude (row TTK_BN_AUX of the BatchNorm block that forms it, include/ttk.h):
-// S = 2^(14 - floor(log2 bound)).  Elements down to 2^-17 of the bound keep all 22 bits; smaller ones keep an ABSOLUTE
-// error of 2^-40 of the bound, far below the fp32 rounding of the elements that dominate a sum.  Bounds come from the
-// statistics the step has anyway (bn.hip: Cauchy-Schwarz on the batch variance forward, the producer's max|g| backward).
-//
-// Structure: as pwconv_split.hip (one workgroup = 8 waves = one CU; waves 4-7 produce - global loads, BatchNorm form,
+// Structure: one workgroup = 8 waves = one CU; waves 4-7 produce - global loads, BatchNorm form,
 // split, ds_write into a ring of 2 x 2 k16 stages; waves 0-3 consume - ds_read_b128 fragments + MFMAs on (BM/2)x(BN/2)
-// wave tiles; one s_barrier per k32), with two piece planes per operand.
+// wave tiles; one s_barrier per k32, with two piece planes per operand.
 #include "ttk_common.h"
 #include "conv_geom.h"
+#include "split16.h"
 #include <type_traits>
 
 namespace ttk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 enum { SMODE_FWD = 0, SMODE_DGRAD = 1 };
 
@@ -52,25 +32,6 @@ constexpr int kStride16 = kStage16 + 64;    // the two k16 halves of a producer 
 #define TTK_DW 1
 #endif
 constexpr int ring_bytes(int rs) { return rs * 2 * kStride16; }
-
-__device__ __forceinline__ int swz16(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 3) & 1)) << 4); }
-
-// 2-piece split of 4 consecutive-k values (already scaled); writes the two 8-byte pieces at dst and dst + plane
-__device__ __forceinline__ void split_store16(f32x4 v, unsigned char* dst, int plane) {
-  const f16x2 h01 = __builtin_convertvector(f32x2{v.x, v.y}, f16x2), h23 = __builtin_convertvector(f32x2{v.z, v.w}, f16x2);
-  const f32x2 f01 = __builtin_convertvector(h01, f32x2), f23 = __builtin_convertvector(h23, f32x2);
-  const f16x2 l01 = __builtin_convertvector(f32x2{v.x - f01.x, v.y - f01.y}, f16x2);
-  const f16x2 l23 = __builtin_convertvector(f32x2{v.z - f23.x, v.w - f23.y}, f16x2);
-  *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-  *reinterpret_cast<uint2*>(dst + plane) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-}
-
-// 4 consecutive activation values as f32x4 (streamed: non-temporal)
-template <typename T>
-__device__ __forceinline__ f32x4 ld_act4(const T* p) {
-  const float4 v = Act<T>::ldnt(p);
-  return f32x4{v.x, v.y, v.z, v.w};
-}
 
 // The consumer side of one block tile: `nks` super-stages (k32) of ds_read_b128 fragments + 3-product MFMAs into
 // acc[TM][TN].  Executes exactly 1 + nks barriers (matching the producers).
@@ -936,11 +897,10 @@ __global__ void w16_split_k(const float* __restrict__ w, uint16_t* __restrict__ 
   const float s = pow2_scale(*wmax);
   const int row = (int)(i / K), k = (int)(i - (int64_t)row * K);
   const int64_t o = ((int64_t)(k >> 5) * rows + row) * 32 + (k & 31);
-  const float x = w[i] * s;
-  const _Float16 hh = (_Float16)x;
-  const _Float16 ll = (_Float16)(x - (float)hh);
-  q[o] = __builtin_bit_cast(uint16_t, hh);
-  q[n + o] = __builtin_bit_cast(uint16_t, ll);
+  uint16_t h, l;
+  split16(w[i] * s, h, l);
+  q[o] = h;
+  q[n + o] = l;
 }
 
 // Returns true when the shape was handled here (and the kernels launched on `st`).  Bm != nullptr: raw weight rows

@@ -1,6 +1,6 @@
 // Pointwise 1x1 convolutions of the wide layers (Cin >= 128, Cout a multiple of 256) - forward and data gradient - as
 // fp32 GEMMs on the fp16 matrix pipe, "row-block" form.  Reference: DepthWiseBlock.conv_sep + bn_sep,
-// backbones/mobilenet_v1.py:67-68,82-84.  Arithmetic, operand bounds and numerics: pwconv_f16.hip (two fp16 pieces per
+// backbones/mobilenet_v1.py:67-68,82-84.  Arithmetic, operand bounds and numerics: split16.h (two fp16 pieces per
 // operand, three v_mfma_f32_32x32x16_f16 per product, fp32 accumulation).
 //
 // What is different from pw16_k, and why (round 3; measurements in DESIGN.md 4.1).  A 128x256 tile moves 16 KB of A (fp32
@@ -20,6 +20,7 @@
 //  * BatchNorm partial sums: one row per tile (ttk_partial_rows_pwconv).
 #include "ttk_common.h"
 #include "conv_geom.h"
+#include "split16.h"
 #include <type_traits>
 
 // TTK_M_NOPK=1 (experiment builds): this file's kernels without packed fp32 instructions.  Measured (profiles/r04_rowblock_gemm_variants.txt):
@@ -33,12 +34,6 @@
 #endif
 
 namespace ttk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 enum { RMODE_FWD = 0, RMODE_DGRAD = 1 };
 // Experiment builds only (tools/exp/build_variants.sh; the product is built with all of them at their defaults):
@@ -127,17 +122,6 @@ __device__ __forceinline__ void rbarrier_s(unsigned long long& wait) {
 }
 #endif
 
-__device__ __forceinline__ int rswz(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 3) & 1)) << 4); }
-
-__device__ __forceinline__ void rsplit_store(f32x4 v, unsigned char* dst, int plane) {
-  const f16x2 h01 = __builtin_convertvector(f32x2{v.x, v.y}, f16x2), h23 = __builtin_convertvector(f32x2{v.z, v.w}, f16x2);
-  const f32x2 f01 = __builtin_convertvector(h01, f32x2), f23 = __builtin_convertvector(h23, f32x2);
-  const f16x2 l01 = __builtin_convertvector(f32x2{v.x - f01.x, v.y - f01.y}, f16x2);
-  const f16x2 l23 = __builtin_convertvector(f32x2{v.z - f23.x, v.w - f23.y}, f16x2);
-  *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-  *reinterpret_cast<uint2*>(dst + plane) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-}
-
 // Low piece l = fp16(x - h) of two values whose high pieces are the halves of `h`: v_fma_mixlo/hi_f16 take the fp16 half as a source
 // of an fp32 fma and round the result to fp16 once - the value of (cvt_f32_f16, subtract, cvt_pk_f16_f32) in two instructions
 // instead of three and a half.  (Vector instructions of an MFMA wave are not free: they cost the matrix pipe a few cycles each.)
@@ -149,16 +133,9 @@ __device__ __forceinline__ unsigned rlow2(unsigned h, float x0, float x1) {
       : "v"(h), "v"(x0), "v"(x1));
   return l;
 }
-template <typename T>
-__device__ __forceinline__ f32x4 rld_act4(const T* p) {
-  const float4 v = Act<T>::ldnt(p);
-  return f32x4{v.x, v.y, v.z, v.w};
-}
 // The producers' row loads as BUFFER loads: a wave-uniform descriptor (rebuilt per k32 step: scalar work) + one 32-bit byte offset
 // per lane.  As global loads hipcc kept a 64-bit address pair per (row pass, tensor) in registers across the loop - 24 VGPRs of the
 // data gradient's producers, which is what made a second set of rows spill.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rbuf(const T* base) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, 0x7fffffff, 0x00020000);
@@ -435,12 +412,12 @@ __global__ void __launch_bounds__(768) pw16r_k(const TO* __restrict__ A0, const 
           const f32x4 t0 = v;
           asm volatile("" ::"v"(t0));
         } else if constexpr (kRDbg & 32) {
-          unsigned char* dst = S + rswz(row0 + 32 * i, chunk);
+          unsigned char* dst = S + swz16(row0 + 32 * i, chunk);
           const f32x4 w = ra0[slot][u];
           *reinterpret_cast<uint2*>(dst) = make_uint2(__float_as_uint(w.x), __float_as_uint(w.y));
           *reinterpret_cast<uint2*>(dst + APL) = make_uint2(__float_as_uint(w.z), __float_as_uint(w.w));
         } else
-        rsplit_store(v, S + rswz(row0 + 32 * i, chunk), APL);
+        split_store16(v, S + swz16(row0 + 32 * i, chunk), APL);
       }
     };
     // Stage s is consumed between barrier s and barrier s + 1 from slot s & 1; meanwhile the producers write the A planes of stage
@@ -494,9 +471,9 @@ __global__ void __launch_bounds__(768) pw16r_k(const TO* __restrict__ A0, const 
     constexpr int HPL = HOLD_A ? APL : BPL, SPL = HOLD_A ? BPL : APL;
     int hold_off[TH], strm_off[TS];
 #pragma unroll
-    for (int x = 0; x < TH; ++x) hold_off[x] = HOLD_A ? rswz(wm * (32 * TM) + x * 32 + r, h) : 2 * APL + rswz(wn * (32 * TN) + x * 32 + r, h);
+    for (int x = 0; x < TH; ++x) hold_off[x] = HOLD_A ? swz16(wm * (32 * TM) + x * 32 + r, h) : 2 * APL + swz16(wn * (32 * TN) + x * 32 + r, h);
 #pragma unroll
-    for (int x = 0; x < TS; ++x) strm_off[x] = HOLD_A ? 2 * APL + rswz(wn * (32 * TN) + x * 32 + r, h) : rswz(wm * (32 * TM) + x * 32 + r, h);
+    for (int x = 0; x < TS; ++x) strm_off[x] = HOLD_A ? 2 * APL + swz16(wn * (32 * TN) + x * 32 + r, h) : swz16(wm * (32 * TM) + x * 32 + r, h);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -699,7 +676,7 @@ __global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const 
   const unsigned aoff0 = (unsigned)(row0 * kCB + kq8 * 4);
   const float* cq = cst + kq8 * 4;
   // LDS destination of pass u in ring slot s: ((row >> 3) & 1 is that of row0: the passes are 64 rows apart)
-  unsigned char* wbase = lds + sub_ * kStr + o8 + rswz(row0, chunk);
+  unsigned char* wbase = lds + sub_ * kStr + o8 + swz16(row0, chunk);
 
   auto load_a = [&](int ks, auto setc) {  // rows of stage ks -> register set
     constexpr int set = decltype(setc)::value;
@@ -776,9 +753,9 @@ __global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const 
   static_assert(2 * TS * TH == 2 * RBLK && 2 * AP == RBLK, "one conversion part behind every second MFMA triple");
   int hold_off[TH], strm_off[TS];
 #pragma unroll
-  for (int x = 0; x < TH; ++x) hold_off[x] = HOLD_A ? rswz(wm * (32 * TM) + x * 32 + r, h) : 2 * APL + rswz(wn * (32 * TN) + x * 32 + r, h);
+  for (int x = 0; x < TH; ++x) hold_off[x] = HOLD_A ? swz16(wm * (32 * TM) + x * 32 + r, h) : 2 * APL + swz16(wn * (32 * TN) + x * 32 + r, h);
 #pragma unroll
-  for (int x = 0; x < TS; ++x) strm_off[x] = HOLD_A ? 2 * APL + rswz(wn * (32 * TN) + x * 32 + r, h) : rswz(wm * (32 * TM) + x * 32 + r, h);
+  for (int x = 0; x < TS; ++x) strm_off[x] = HOLD_A ? 2 * APL + swz16(wn * (32 * TN) + x * 32 + r, h) : swz16(wm * (32 * TM) + x * 32 + r, h);
   if constexpr (!M16) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -799,9 +776,9 @@ __global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const 
   if constexpr (M16) {
     const int r16 = lane & 15, g4 = lane >> 4;
 #pragma unroll
-    for (int i = 0; i < 2 * TM; ++i) a16_off[i] = (g4 >> 1) * kStr + rswz(wm * (32 * TM) + i * 16 + r16, g4 & 1);
+    for (int i = 0; i < 2 * TM; ++i) a16_off[i] = (g4 >> 1) * kStr + swz16(wm * (32 * TM) + i * 16 + r16, g4 & 1);
 #pragma unroll
-    for (int j = 0; j < 2 * TN; ++j) b16_off[j] = (g4 >> 1) * kStr + 2 * APL + rswz(wn * (32 * TN) + j * 16 + r16, g4 & 1);
+    for (int j = 0; j < 2 * TN; ++j) b16_off[j] = (g4 >> 1) * kStr + 2 * APL + swz16(wn * (32 * TN) + j * 16 + r16, g4 & 1);
   }
   // LDS-DMA of the weight planes (as pw16r_k): wave w moves pieces 4 w .. 4 w + 3 of a k32 step - k16 stage w >> 2, plane (w >> 1) & 1,
   // rows 128 (w & 1) .. + 127 - right after the barrier that freed the slot, and waits for them before the barrier that publishes it.
@@ -1035,23 +1012,15 @@ constexpr int kTPlane = 16 * kTRow;              // one piece plane of one opera
 constexpr int kTStage = 4 * kTPlane;             // [dy h][dy l][a h][a l]
 constexpr int kTRing = 2 * 2 * kTStage;          // two k32 super-stages
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x8 tr_frag(const unsigned char* plane, int off) {
   // rows 8h .. 8h+3 and 8h+4 .. 8h+7 of the stage (the lane's address already holds 8h + q): element j = 4 t + q' of the fragment
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(plane + off));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(plane + off + 4 * kTRow));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(f16x8, v);
 }
-__device__ __forceinline__ void tsplit_store(f32x4 v, unsigned char* dst) {  // 4 consecutive channels of one m-row: h at dst, l at dst + kTPlane
-  const f16x2 h01 = __builtin_convertvector(f32x2{v.x, v.y}, f16x2), h23 = __builtin_convertvector(f32x2{v.z, v.w}, f16x2);
-  const f32x2 f01 = __builtin_convertvector(h01, f32x2), f23 = __builtin_convertvector(h23, f32x2);
-  const f16x2 l01 = __builtin_convertvector(f32x2{v.x - f01.x, v.y - f01.y}, f16x2);
-  const f16x2 l23 = __builtin_convertvector(f32x2{v.z - f23.x, v.w - f23.y}, f16x2);
-  *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-  *reinterpret_cast<uint2*>(dst + kTPlane) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-}
+// 4 consecutive channels of one m-row: h at dst, l at dst + kTPlane
+__device__ __forceinline__ void tsplit_store(f32x4 v, unsigned char* dst) { split_store16(v, dst, kTPlane); }
 
 #if defined(TTK_EXPERIMENTS)  // (pw16t_wgrad_k is selectable by TTK_WGRAD_T=t only: ahead of pw16u_wgrad_k on no shape but 1024 x 1024, and there by 5 %)
 // G, Y: [M][Cout] (gradient w.r.t. the BatchNorm output, raw conv output), X: [M][Cin] (raw depthwise output); partial[slice][Cout][Cin]
@@ -1096,9 +1065,9 @@ __global__ void __launch_bounds__(768) pw16t_wgrad_k(const TG* __restrict__ G, c
     auto load_row = [&](int ks, int i) {
       int64_t row = r0 + (int64_t)ks * 32 + i;
       row = row < m_end ? row : m_end - 1;  // (rows past the slice are zeroed when they are stored)
-      rg[i] = rld_act4<TG>(G + act_off(row, ca, M));
-      ry[i] = rld_act4<T>(Y + act_off(row, ca, M));
-      rx[i] = rld_act4<T>(X + act_off(row, cb, M));
+      rg[i] = ld_act4<TG>(G + act_off(row, ca, M));
+      ry[i] = ld_act4<T>(Y + act_off(row, ca, M));
+      rx[i] = ld_act4<T>(X + act_off(row, cb, M));
     };
     auto store = [&](int ks) {  // the eight rows of step ks: BatchNorm backward / BatchNorm + ReLU, split, to LDS
       unsigned char* dy = wdy + (ks & 1) * 2 * kTStage;
@@ -1251,14 +1220,14 @@ __global__ void __launch_bounds__(768) pw16u_wgrad_k(const TG* __restrict__ G, c
       for (int i = 0; i < 4; ++i) {
         int64_t row = rb + i;
         row = row < m_end ? row : m_end - 1;  // (rows past the slice are zeroed when they are stored)
-        rx[set][i] = rld_act4<T>(X + ob + (size_t)row * kCB);
+        rx[set][i] = ld_act4<T>(X + ob + (size_t)row * kCB);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         int64_t row = rb + ra + j;
         row = row < m_end ? row : m_end - 1;
-        rg[set][j] = rld_act4<TG>(G + oa + (size_t)row * kCB);
-        ry[set][j] = rld_act4<T>(Y + oa + (size_t)row * kCB);
+        rg[set][j] = ld_act4<TG>(G + oa + (size_t)row * kCB);
+        ry[set][j] = ld_act4<T>(Y + oa + (size_t)row * kCB);
       }
     };
     auto store = [&](int ks, auto setc) {  // BatchNorm backward / BatchNorm + ReLU, split, to LDS
@@ -1487,11 +1456,10 @@ __global__ void w16r_split_k(const float* __restrict__ w, uint16_t* __restrict__
   const float s = pow2_scale(*wmax);
   const int row = (int)(i / K), k = (int)(i - (int64_t)row * K);
   const int64_t o = r_plane_index(row, k, rows);
-  const float x = w[i] * s;
-  const _Float16 hh = (_Float16)x;
-  const _Float16 ll = (_Float16)(x - (float)hh);
-  q[o] = __builtin_bit_cast(uint16_t, hh);
-  q[n + o] = __builtin_bit_cast(uint16_t, ll);
+  uint16_t h, l;
+  split16(w[i] * s, h, l);
+  q[o] = h;
+  q[n + o] = l;
 }
 __global__ void __launch_bounds__(256) w16r_absmax_k(const float* __restrict__ w, int64_t n, unsigned* __restrict__ wmax) {
   float m = 0.f;

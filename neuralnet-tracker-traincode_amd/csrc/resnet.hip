@@ -5,6 +5,7 @@
 // the dense 3x3 / 1x1 convolutions are in conv.hip.
 #include "ttk_common.h"
 #include "stem_wgrad.h"
+#include "split16.h"
 #include <stdlib.h>
 
 namespace ttk {
@@ -97,7 +98,6 @@ __global__ void __launch_bounds__(kBlock) stem7_fwd_k(const float* __restrict__ 
 // input rows its pixels touch are staged in a private LDS patch [9][Wp] (zero padded), MFMA j multiplies the pixels'
 // values under taps 2j, 2j+1 (lanes 0-31 | 32-63: one ds_read_b32 each, conflict-free at stride 2) with the two filter
 // rows held in registers.  Wave-private LDS: no workgroup barrier in the loop; groups go round-robin over all waves.
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 __global__ void __launch_bounds__(kBlock) stem7_fwd_mfma_k(const float* __restrict__ x, const float* __restrict__ w,
                                                             float* __restrict__ y, float* __restrict__ part, const float* __restrict__ pivot,
                                                             int B, int H, int W, int Ho, int Wo, int PR, int wave_floats) {
@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(kBlock) stem7_fwd_mfma_k(const float* __restri
     const int p = p0 + px;
     const int pc = p < hw ? p : hw - 1, oh = pc / Wo, ow = pc - oh * Wo;
     const float* win = patch + (2 * (oh - oh0)) * Wp + 2 * ow;
-    f32x16_t acc0, acc1;
+    f32x16 acc0, acc1;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
 #pragma unroll
@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(kBlock) stem7_wgrad_mfma_k(const float* __rest
   const int c4 = lane & 15, prow = lane >> 4;  // dy staging: 16 lanes x float4 = one pixel's 64 channels
   const float4 ga = ld4(bn + TTK_BN_GA * kS7C + 4 * c4), gb = ld4(bn + TTK_BN_GB * kS7C + 4 * c4);
   const float4 gmean = ld4(bn + TTK_BN_GMEAN * kS7C + 4 * c4), mean = ld4(bn + TTK_BN_MEAN * kS7C + 4 * c4);
-  f32x16_t acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -478,18 +478,9 @@ __global__ void __launch_bounds__(kBlock) stem7_wgrad_mfma_k(const float* __rest
 
 // dy = ga*(g-gmean) + gb*(y-mean): the gradient w.r.t. a conv output through its BatchNorm, written once for the
 // convolution's weight and data gradients (both then read 4 instead of 8 bytes per element, the data gradient nine times).
-// Written as the fp16-split GEMMs consume it (pwconv_f16.hip): two fp16 planes [rows][C] - h = fp16(dy S), then l = fp16(dy S - h),
+// Written as the fp16-split GEMMs consume it (split16.h): two fp16 planes [rows][C] - h = fp16(dy S), then l = fp16(dy S - h),
 // S = pow2_scale(bn[TTK_BN_AUX][TTK_AUX_DY_BOUND]) - the same 4 bytes per element as fp32, and the GEMM producers move them
 // without arithmetic.  thread = (row, 8 channels): one 16-byte store per plane.
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split2(float a, float b, unsigned& h, unsigned& l) {
-  const f16x2_t hh = __builtin_convertvector(f32x2_t{a, b}, f16x2_t);
-  const f32x2_t back = __builtin_convertvector(hh, f32x2_t);
-  const f16x2_t ll = __builtin_convertvector(f32x2_t{a - back.x, b - back.y}, f16x2_t);
-  h = __builtin_bit_cast(unsigned, hh);
-  l = __builtin_bit_cast(unsigned, ll);
-}
 __global__ void __launch_bounds__(kBlock) bn_bwd_apply_k(const float* __restrict__ g, const float* __restrict__ y,
                                                           const float* __restrict__ bnp, uint16_t* __restrict__ dy, int64_t items, int C) {
   const int octs = C >> 3;
@@ -513,7 +504,7 @@ __global__ void __launch_bounds__(kBlock) bn_bwd_apply_k(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = ga[j] * (gv[j] - gmean[j]) + gb[j] * (yv[j] - mean[j]);
     uint4 h, l;
-    split2(v[0], v[1], h.x, l.x); split2(v[2], v[3], h.y, l.y); split2(v[4], v[5], h.z, l.z); split2(v[6], v[7], h.w, l.w);
+    split16x2(v[0], v[1], h.x, l.x); split16x2(v[2], v[3], h.y, l.y); split16x2(v[4], v[5], h.z, l.z); split16x2(v[6], v[7], h.w, l.w);
     *reinterpret_cast<uint4*>(dy + off) = h;
     *reinterpret_cast<uint4*>(lo + off) = l;
   }

@@ -9,7 +9,6 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 BN_SCALE, BN_BETA, BN_MEAN, BN_RSTD, BN_GA, BN_GB, BN_GMEAN, BN_AUX = range(8)
 AUX_ACT_BOUND, AUX_DY_BOUND, AUX_GMAX = 0, 1, 2
-F16 = __import__("os").environ.get("TTK_GEMM") != "bf16x3"  # the default fp16-pipe kernels (bounds, materialised dy, slice-wise weight gradient)
 
 
 def _bn_block(C, rng):
@@ -100,8 +99,7 @@ def test_conv_fwd_bwd_data_bwd_weight(B, H, Cin, Cout, k, stride):
         torch.cuda.synchronize()
         out = g_in.cpu().numpy()
         assert _rel(out * safe, ref * safe) < 1.5e-6
-        if F16:
-            assert float(d_mbn[BN_AUX, AUX_GMAX]) == float(np.abs(out).max())  # the bound of the next layer's gradient operand
+        assert float(d_mbn[BN_AUX, AUX_GMAX]) == float(np.abs(out).max())  # the bound of the next layer's gradient operand
         ps = part2.cpu().numpy().astype(np.float64)
         o64 = out.astype(np.float64).reshape(-1, Cin)
         np.testing.assert_allclose(ps[:, 0].sum(0), o64.sum(0), rtol=0, atol=3e-5 * np.abs(o64).sum(0).max())
@@ -113,8 +111,6 @@ def test_conv_fwd_bwd_data_bwd_weight(B, H, Cin, Cout, k, stride):
     L.call("ttk_conv_bwd_weight", p(d_g), p(y), p(d_bn), p(d_a), p(a_bound), p(dw), None, B, H, W, Cin, Cout, k, k, stride, pad)
     torch.cuda.synchronize()
     assert _rel(dw.cpu().numpy(), gw_ref.numpy()) < 1.5e-6
-    if not F16:
-        return
 
     # ---- the same two gradients from a materialised dy (ttk_bn_bwd_apply; y == NULL)
     d_dy = torch.empty_like(d_g)

@@ -1,7 +1,7 @@
 """GPU parity of the pointwise-conv GEMM entry points (C-ABI) against float64 numpy.
 
-The compute-bound shapes run on the 16-bit matrix pipe with split operands (csrc/pwconv_f16.hip: two fp16 pieces and
-three products, scaled by the magnitude bounds of row TTK_BN_AUX; TTK_GEMM=bf16x3: csrc/pwconv_split.hip); the criterion
+The compute-bound shapes run on the 16-bit matrix pipe with split operands (csrc/split16.h, csrc/pwconv_f16.hip: two fp16
+pieces and three products, scaled by the magnitude bounds of row TTK_BN_AUX); the criterion
 is that they are as close to the exact product as a chain of fp32 multiply-adds over the same operands is (one fp32
 accumulator per output, k by k) - i.e. no precision was given up for the speed."""
 import numpy as np
@@ -46,8 +46,8 @@ SHAPES = [(648, 512, 512), (1000, 128, 256), (4100, 256, 256), (300, 1024, 1024)
           # row-block kernels (csrc/pwconv_r.hip) at tile heights their cost model picks by itself: 162 of 192 rows (two column tiles:
           # one full round of 256 CUs), 200 of 256 rows, 193-row blocks with a ragged last one
           (20736, 512, 512), (12800, 256, 1024), (49601, 128, 256),
-          # the streaming kernel of the narrow layers (csrc/pwconv_y.hip: 32 -> 64, 64 -> 128, 128 -> 128 forward; data gradient of 128 -> 256): more pixel
-          # groups than resident waves, a ragged last group, fewer groups than waves
+          # the narrow HBM-bound layers (32 -> 64, 64 -> 128, 128 -> 128; data gradient of 128 -> 256) at long, ragged and very short M: more tiles than
+          # resident workgroups, a ragged last tile, a single tile
           (140001, 32, 64), (99990, 64, 128), (70001, 128, 128), (33, 64, 128), (41111, 128, 256)]
 
 

@@ -1,5 +1,5 @@
 """GPU micro-benchmark of the three implicit-GEMM convolution entry points on the conv shapes of the ResNet18 variant at
-batch B (129x129 input).  python tools/bench_conv.py [B] [iters]     (TTK_GEMM=bf16x3 for the previous kernels)"""
+batch B (129x129 input).  python tools/bench_conv.py [B] [iters]     (ONLOAD=1: the gradients form dy on load instead of reading a materialised one)"""
 import os
 import sys
 
@@ -34,7 +34,7 @@ for name, hw, ci, co, k, s, mult in shapes:
     dy = torch.empty_like(g)
     nb = L.conv_wgrad_partial_bytes(B, hw, hw, ci, co, k, s)
     scr = torch.empty(nb // 4, device=dev) if nb and not os.environ.get("ATOMIC") else None  # slice-wise weight gradient (ATOMIC=1: fp32 atomics)
-    yp = p(y) if os.environ.get("TTK_GEMM") == "bf16x3" or os.environ.get("ONLOAD") else None  # None: the gradients read the materialised dy
+    yp = p(y) if os.environ.get("ONLOAD") else None  # None: the gradients read the materialised dy
     wf, wb = torch.empty(3, k * k, co, ci, dtype=torch.int16, device=dev), torch.empty(3, k * k, ci, co, dtype=torch.int16, device=dev)
     L.call("ttk_conv_weight_repack", p(w), p(wf), p(wb), co, ci, k, k)
     out, gin, dw = torch.empty(B, ho, ho, co, device=dev), torch.empty(B, hw, hw, ci, device=dev), torch.zeros(co, ci, k, k, device=dev)

@@ -14,6 +14,7 @@ while [ $# -ge 3 ]; do
   name=$1; src=$2; defs=$3; shift 3
   (
     base=$(basename $src .hip)
+    case $base in heads|losses) defs="$defs -fno-slp-vectorize";; esac  # as the product compiles these two (csrc/Makefile: FLAGS_heads, FLAGS_losses)
     /opt/rocm/bin/hipcc $FLAGS $defs -I$R/include -c $C/$src -o $O/${base}_$name.o
     objs=$(ls $C/build/*.o | grep -v "/$base.o")
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs $O/${base}_$name.o -o $O/libttk_$name.so
