@@ -82,15 +82,15 @@ enum {
  *                                                         (ttk_avgpool_bwd, ttk_dwconv3x3_bwd_data)
  *   DY_BOUND  >= max |ga*(g-gmean) + gb*(y-mean)|         written by ttk_bn_bwd_finalize from GMAX and the variance */
 enum { TTK_AUX_ACT_BOUND = 0, TTK_AUX_DY_BOUND = 1, TTK_AUX_GMAX = 2 };
-/* Storage of the activation-sized tensors of the MobileNet path.  Entry points with an `act_bf16` argument take them as
- * `void*`; the argument is a set of TTK_STORE_* bits:
- *   0                                      everything float32 - the reference's precision: what the depthwise (ttk_dwconv3x3_*),
- *                                          pointwise (ttk_pwconv1x1_*) and pooling (ttk_avgpool_*) entry points accept.  The storage-only
- *                                          bf16 variants of rounds 2-5 (`--precision bf16 | bf16-all`) are RETIRED: those entry points
- *                                          return -1 for either bit and name the bf16-compute path (ttk_bc_*, below)
- *   TTK_STORE_ACT_BF16|TTK_STORE_GRAD_BF16 activations AND gradients bfloat16: accepted by the stem pair only (ttk_stem_fwd,
- *                                          ttk_stem_bwd_weight), which also serves the bf16-compute path (C = 32: same bytes in either
- *                                          block layout).  Rounded to nearest even on store; BatchNorm statistics from the values as stored. */
+/* Storage of the activation-sized tensors of the MobileNet path: the `act_bf16` argument, a set of TTK_STORE_* bits.
+ *   The depthwise (ttk_dwconv3x3_*), pointwise (ttk_pwconv1x1_*) and pooling (ttk_avgpool_*) entry points are float32 only - the
+ *   reference's precision - and declare their tensors `float*`.  They keep the argument for ABI stability and it must be 0 there
+ *   (apart from the TTK_LAYOUT_* bits of the pooling pair, below): for either storage bit they return -1 from their argument checks,
+ *   before anything is launched or written, and name the bf16-compute path (ttk_bc_*, below).  (The storage-only bf16 variants of
+ *   rounds 2-5, `--precision bf16 | bf16-all`, are RETIRED.)
+ *   The stem pair (ttk_stem_fwd, ttk_stem_bwd_weight: `void*` tensors) also serves the bf16-compute path (C = 32: same bytes in either
+ *   block layout) and takes 0 or TTK_STORE_ACT_BF16|TTK_STORE_GRAD_BF16 - activations AND gradients bfloat16, rounded to nearest even
+ *   on store, BatchNorm statistics from the values as stored. */
 #define TTK_STORE_ACT_BF16 1
 #define TTK_STORE_GRAD_BF16 2
 /* The two entry points both backbones share (ttk_avgpool_fwd / ttk_avgpool_bwd) take this bit in the same argument: their
@@ -180,8 +180,8 @@ int ttk_stem_bwd_weight(const void* g, const void* y, const float* bn, const flo
  * a_out (nullable): materialise a_in, needed when THIS block has a residual connection
  * (mobilenet_v1.py:70,86-88).  w is the reference's weight (C,1,3,3) as is.
  * ------------------------------------------------------------------------------------------- */
-int ttk_dwconv3x3_fwd(const void* yprev, const float* bn_prev, const void* skip_prev, void* a_out,
-                      const float* w, void* y, float* part, const float* pivot, int B, int H, int W, int C,
+int ttk_dwconv3x3_fwd(const float* yprev, const float* bn_prev, const float* skip_prev, float* a_out,
+                      const float* w, float* y, float* part, const float* pivot, int B, int H, int W, int C,
                       int stride, int act_bf16, ttk_stream_t stream);
 /* Gradient w.r.t. the block input, masked by relu and handed to the producer's BatchNorm:
  *   G      = convT3x3(dy_dw) (+ skip_grad)        dy_dw formed on load from (g_dw, y_dw, bn_dw)
@@ -193,9 +193,9 @@ int ttk_dwconv3x3_fwd(const void* yprev, const float* bn_prev, const void* skip_
  * dw_partial (nullable): scratch of ttk_partial_rows_dwconv(.., 1) * 9 * C floats - the fused weight gradient is then
  * folded from per-workgroup rows in a fixed order (bitwise reproducible) instead of fp32 atomics.  * dw_accumulate == 2 (with dw_partial): the rows stay UNFOLDED in dw_partial and the caller folds them with ttk_bc_bn_bwd_finalize_fold, in the
  * launch that finalises the producer's BatchNorm backward (the product's default since round 5: one launch instead of float atomics). */
-int ttk_dwconv3x3_bwd_data(const void* g_dw, const void* y_dw, const float* bn_dw, const float* w,
-                           const void* skip_grad, const void* yprev, float* bn_prev,
-                           const void* skip_prev, const void* a_in, void* g_prev, float* part,
+int ttk_dwconv3x3_bwd_data(const float* g_dw, const float* y_dw, const float* bn_dw, const float* w,
+                           const float* skip_grad, const float* yprev, float* bn_prev,
+                           const float* skip_prev, const float* a_in, float* g_prev, float* part,
                            float* dw, int dw_accumulate, float* dw_partial, int B, int H, int W, int C,
                            int stride, int act_bf16, ttk_stream_t stream);
 
@@ -209,12 +209,12 @@ int ttk_dwconv3x3_bwd_data(const void* g_dw, const void* y_dw, const float* bn_d
  * wsplit (forward and data gradient): scratch of ttk_pwconv_prepared_bytes(Cin, Cout) for the split weight operand,
  * or a block that ttk_pwconv_prepare_weights filled (then w / wt == NULL); NULL selects the fp32 MFMA kernels.
  * ------------------------------------------------------------------------------------------- */
-int ttk_pwconv1x1_fwd(const void* ydw, const float* bn_dw, const float* w, void* y, float* part, const float* pivot,
+int ttk_pwconv1x1_fwd(const float* ydw, const float* bn_dw, const float* w, float* y, float* part, const float* pivot,
                       int64_t M, int Cin, int Cout, void* wsplit, int act_bf16, ttk_stream_t stream);
 /* g_dw[M][Cin] = (dy[M][Cout] . w[Cout][Cin]) * [bn_dw(ydw) > 0],  dy formed on load from (g, y, bn_pw);
  * wt = w transposed ([Cin][Cout], ttk_transpose).  partials: sum(g_dw), sum(g_dw*(ydw-mean)). */
-int ttk_pwconv1x1_bwd_data(const void* g, const void* y, const float* bn_pw, const float* wt,
-                           const void* ydw, const float* bn_dw, void* g_dw, float* part, int64_t M,
+int ttk_pwconv1x1_bwd_data(const float* g, const float* y, const float* bn_pw, const float* wt,
+                           const float* ydw, const float* bn_dw, float* g_dw, float* part, int64_t M,
                            int Cin, int Cout, void* wsplit, int act_bf16, ttk_stream_t stream);
 /* dw[Cout][Cin] += dy^T . a_dw.  dw must be zeroed (or hold the running gradient) before the call.
  * partial == NULL: the M dimension is split over workgroups that add atomically (fp32 atomics: the result depends on
@@ -225,7 +225,7 @@ int ttk_pwconv1x1_bwd_data(const void* g, const void* y, const float* bn_pw, con
  * for a shape (0: none, the atomic form runs). */
 size_t ttk_pwconv_wgrad_partial_bytes(int64_t M, int Cin, int Cout);
 size_t ttk_pwconv_wgrad_scratch_bytes(int64_t M, int Cin, int Cout);
-int ttk_pwconv1x1_bwd_weight(const void* g, const void* y, const float* bn_pw, const void* ydw,
+int ttk_pwconv1x1_bwd_weight(const float* g, const float* y, const float* bn_pw, const float* ydw,
                              const float* bn_dw, float* dw, float* partial, int64_t M, int Cin, int Cout,
                              int act_bf16, ttk_stream_t stream);
 /* Weight operands of n (<= 16) pointwise layers (w[i]: [Cout][Cin] fp32 device pointers; w, cin, cout and
@@ -256,11 +256,11 @@ int ttk_transpose(const float* in, float* out, int rows, int cols, ttk_stream_t 
  * AdaptiveAvgPool2d(1) + view over the last block's output - mobilenet_v1.py:143,180-181.
  *   feat[B][C] = mean_hw max(bn(y) (+ skip), 0)
  * ------------------------------------------------------------------------------------------- */
-int ttk_avgpool_fwd(const void* y, const float* bn, const void* skip, float* feat, int B, int HW,
+int ttk_avgpool_fwd(const float* y, const float* bn, const float* skip, float* feat, int B, int HW,
                     int C, int act_bf16, ttk_stream_t stream);
 /* g[B][HW][C] = gfeat[B][C]/HW * [bn(y)+skip > 0]; partials sum(g), sum(g*(y-mean)); raises
  * bn[TTK_BN_AUX][TTK_AUX_GMAX] to max |g|. */
-int ttk_avgpool_bwd(const float* gfeat, const void* y, float* bn, const void* skip, void* g,
+int ttk_avgpool_bwd(const float* gfeat, const float* y, float* bn, const float* skip, float* g,
                     float* part, int B, int HW, int C, int act_bf16, ttk_stream_t stream);
 /* a[rows][C] = max(bn(y) (+ skip), 0): materialises a post-activation tensor (the `intermediates` list
  * MobileNet.forward returns, mobilenet_v1.py:165-186).  y, skip: channel blocks; a: plain channels-last rows. */

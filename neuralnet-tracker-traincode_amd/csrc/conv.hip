@@ -11,18 +11,8 @@ namespace ttk {
 
 // w[Cout][Cin][T] (torch layout, T = KH*KW) -> wf[2][T][Cout][Cin] (forward B operand, N = Cout, K = (t, ci)) and wb[2][T][Cin][Cout] (data
 // gradient, N = Cin, K = (t, co)): the fp16 piece planes h, l in the GEMMs' [K/32][N][32] order, K = (tap, channel) with the channel
-// fastest, so that the GEMM producers move the weight operand without arithmetic.  First max |w| (ordered-uint atomicMax into *wmax,
-// zeroed by the caller), then the two planes of w * pow2_scale(max), each followed by a copy of the maximum (the header the GEMMs read
+// fastest, so that the GEMM producers move the weight operand without arithmetic.  First max |w| (w16_absmax_k, split16.h), then the two planes of w * pow2_scale(max), each followed by a copy of the maximum (the header the GEMMs read
 // their scale from).
-__global__ void __launch_bounds__(256) conv_weight_absmax_k(const float* __restrict__ w, int64_t n, unsigned* __restrict__ wmax) {
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __hip_atomic_load(wmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMax(wmax, __float_as_uint(m));
-}
-
 __global__ void conv_weight_repack16_k(const float* __restrict__ w, uint16_t* __restrict__ wf, uint16_t* __restrict__ wb,
                                        const float* __restrict__ wmax, int Cout, int Cin, int T) {
   const int64_t n = (int64_t)Cout * Cin * T;
@@ -156,9 +146,7 @@ int ttk_conv_weight_repack(const float* w, void* w_fwd, void* w_bwd, int Cout, i
   TTK_REQUIRE_CONV_F16("conv_weight_repack");
   const int64_t n = (int64_t)Cout * Cin * KH * KW;
   float* hdr = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(w_fwd ? w_fwd : w_bwd) + 2 * n);  // behind the two planes
-  (void)hipMemsetAsync(hdr, 0, sizeof(float), (hipStream_t)stream);
-  hipLaunchKernelGGL(conv_weight_absmax_k, dim3((unsigned)(n / 1024 < 1 ? 1 : (n / 1024 > 256 ? 256 : n / 1024))), dim3(256), 0,
-                     (hipStream_t)stream, w, n, reinterpret_cast<unsigned*>(hdr));
+  launch_w16_absmax(w, n, hdr, (hipStream_t)stream);
   hipLaunchKernelGGL(conv_weight_repack16_k, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, w, (uint16_t*)w_fwd,
                      (uint16_t*)w_bwd, hdr, Cout, Cin, KH * KW);
   TTK_LAUNCH_CHECK("conv_weight_repack");

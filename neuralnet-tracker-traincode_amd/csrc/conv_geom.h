@@ -50,7 +50,19 @@ inline int gemm_mode() {
 __host__ __device__ inline size_t prep_bwd_offset(size_t n) { return 4 * n; }
 __host__ __device__ inline size_t prep_hdr_offset(size_t n) { return 8 * n; }
 
-// fp16-pipe forms (pwconv_f16.hip): Bq = two fp16 planes scaled by pow2_scale(*wmax); a_bound = bound of a plain A operand
+// ---- launchers and shape predicates of the pointwise GEMM files, declared once (MODE: 0 forward, 1 data gradient) ----
+// A `bool` launcher returns false when the shape is not its own (nothing launched) - the caller falls through to the next form.
+
+// pwconv_f16.hip: the compute-bound shapes on the fp16 pipe with 2-piece operand splits (three products) - the default
+template <int MODE>
+bool launch_f16_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0, const float* bnE,
+                     float* part, int64_t M, int K, int Nout, void* planes, float* wmax, hipStream_t st);
+bool f16_gemm_shape(int K, int Nout);
+bool launch_f16_wgrad(const float* g, const float* y, const float* bn_pw, const float* ydw, const float* bn_dw, float* dw, float* partial,
+                      int64_t M, int Cin, int Cout, hipStream_t st);
+size_t f16_wgrad_partial_bytes(int64_t M, int Cin, int Cout);
+
+// the convolutions' forms (conv.hip): Bq = two fp16 planes scaled by pow2_scale(*wmax); a_bound = bound of a plain A operand
 bool launch_conv_gemm16(int amode, int emode, const float* A0, const float* A1, const float* bnA, const float* a_bound, const uint16_t* Bq,
                         const float* wmax, float* out, const float* E0, float* bnE, float* part, int64_t M, int K, int Nout,
                         const ConvGeom& geo, hipStream_t st);
@@ -64,8 +76,19 @@ __host__ __device__ inline int64_t r_plane_index(int row, int k, int rows) {
   return ((int64_t)(k >> 4) * rows + row) * 16 + ((((k >> 3) & 1) ^ ((row >> 3) & 1)) << 3) + (k & 7);
 }
 
+// pwconv_r.hip: the wide layers (K >= 128, Nout a multiple of 256) in row-block form: 8 consumer waves, variable tile height,
+// LDS-DMA weight planes in the [K/16][Nout][16] layout above
+template <int MODE>
+bool launch_f16r_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0, const float* bnE,
+                      float* part, int64_t M, int K, int Nout, void* planes, float* wmax, hipStream_t st);
 bool f16r_gemm_shape(int K, int Nout, int dgrad);
 int f16r_partial_rows(int64_t M, int K, int Nout, int dgrad);
 int f16r_tile_rows(int64_t M, int K, int Nout, int dgrad);
+
+// pwconv_r.hip: weight gradient of the layers with Cin, Cout multiples of 256 on 256 x 256 tiles with transposed LDS fragment reads; always
+// reduces through `partial` (scratch of f16t_wgrad_scratch_bytes) and a fixed-order fold
+bool launch_f16t_wgrad(const float* g, const float* y, const float* bn_pw, const float* ydw, const float* bn_dw, float* dw, float* partial,
+                       int64_t M, int Cin, int Cout, hipStream_t st);
+size_t f16t_wgrad_scratch_bytes(int64_t M, int Cin, int Cout);
 
 }  // namespace ttk

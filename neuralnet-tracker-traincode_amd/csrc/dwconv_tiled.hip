@@ -13,7 +13,9 @@
 // Workgroups are persistent over tiles of ONE channel slab, so per-channel BatchNorm partial sums and
 // the fused depthwise weight gradient accumulate in registers across tiles and leave the block once
 // (one partial row + 288 float atomics per workgroup).
+// Tensors are float32 in and out (the entry points' storage flag must be 0: ttk.h).
 #include "ttk_common.h"
+#include <type_traits>
 #ifndef TTK_DW_FWD_U
 #define TTK_DW_FWD_U 6
 #endif
@@ -217,11 +219,11 @@ __device__ __forceinline__ void slab_partials(D4 s1, D4 s2, int q, int C, int c_
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-template <int S, typename T, bool SKIP, int SL, bool CARRY>
+template <int S, bool SKIP, int SL, bool CARRY>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_DW_WGS_PER_CU, TTK_DW_WGS_PER_CU)))
-dw_fwd_tiled_k(const T* __restrict__ yprev, const float* __restrict__ bn_prev,
-                                                          const T* __restrict__ skip_prev, T* __restrict__ a_out,
-                                                          const float* __restrict__ w, T* __restrict__ y,
+dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_prev,
+                                                          const float* __restrict__ skip_prev, float* __restrict__ a_out,
+                                                          const float* __restrict__ w, float* __restrict__ y,
                                                           float* __restrict__ part, const float* __restrict__ pivot, int B, int H, int W, int C,
                                                           int Ho, int Wo, int R, int nbands, int nslabs, int NI_, int NCT_, int TW) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [NI][stage_rows][tile width + 2][SL] + reduction scratch
@@ -263,10 +265,10 @@ dw_fwd_tiled_k(const T* __restrict__ yprev, const float* __restrict__ bn_prev,
     // (the bases are uniform over the workgroup - scalar registers; the lane's channel quad rides in the 32-bit offset)
     // channel block `slab` of the input / output tensor, first pixel of image n0: everything this tile touches is one contiguous run
     const size_t tin = ((size_t)slab * B * H * W + (size_t)n0 * H * W) * kCB, tout = ((size_t)slab * B * Ho * Wo + (size_t)n0 * Ho * Wo) * kCB;
-    const T* ytile = yprev + tin;
-    const T* sktile = SKIP ? skip_prev + tin : nullptr;
-    T* aotile = a_out ? a_out + tin : nullptr;
-    T* youttile = y + tout;
+    const float* ytile = yprev + tin;
+    const float* sktile = SKIP ? skip_prev + tin : nullptr;
+    float* aotile = a_out ? a_out + tin : nullptr;
+    float* youttile = y + tout;
     // carry mode: rows i0 .. i0 + OV - 1 of this band are the last OV staged rows of the previous one
     const int ov = (carry && (int)ti == prev_img && band == prev_band + 1) ? OV : 0;
     // a materialised block input (a_out) is stored by whoever STAGES a row: the row below this band too when the next band will take it over
@@ -308,8 +310,8 @@ dw_fwd_tiled_k(const T* __restrict__ yprev, const float* __restrict__ bn_prev,
         rows[u] = (row >= o0 && row < own_hi && col >= cx0 && col < cx0 + tw) ? 1 : 0;  // the one tile this input pixel belongs to
         in[u] = ee < nstage && row >= 0 && row < H && col >= 0 && col < W;
         off[u] = in[u] ? ((__umul24(__umul24(img, (unsigned)H) + (unsigned)row, (unsigned)W) + (unsigned)col) << cshift) + 4 * q : 0u;  // qq == q: kBlock is a multiple of 8
-        yv[u] = in[u] ? Act<T>::ldnt(ytile + off[u]) : f4(0.f);
-        if constexpr (SKIP) sk[u] = in[u] ? Act<T>::ldnt(sktile + off[u]) : f4(0.f);
+        yv[u] = in[u] ? ld4nt(ytile + off[u]) : f4(0.f);
+        if constexpr (SKIP) sk[u] = in[u] ? ld4nt(sktile + off[u]) : f4(0.f);
       }
 #pragma unroll
       for (int u = 0; u < kFwdU; ++u) {
@@ -319,8 +321,7 @@ dw_fwd_tiled_k(const T* __restrict__ yprev, const float* __restrict__ bn_prev,
         if (in[u]) {
           if constexpr (SKIP) a = bn.act(yv[u], sk[u]);
           else a = bn.act(yv[u]);
-          if (S == 1 && a_out) a = Act<T>::round(a);  // a materialised block input is used as it is stored (residual, backward)
-          if (S == 1 && a_out && rows[u]) Act<T>::st(aotile + off[u], a);
+          if (S == 1 && a_out && rows[u]) st4(aotile + off[u], a);  // a materialised block input (residual, backward)
         }
         st4(lds + (size_t)pxs[u] * kSlab + 4 * q, a);
       }
@@ -340,8 +341,7 @@ dw_fwd_tiled_k(const T* __restrict__ yprev, const float* __restrict__ bn_prev,
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) acc = fma4(ld4(base + ((size_t)kh * Wp + kw) * kSlab), wr.tap(kh * 3 + kw), acc);
-      acc = Act<T>::round(acc);  // statistics of what is stored
-      Act<T>::st(youttile + ((__umul24(__umul24(img, (unsigned)Ho) + (unsigned)ho, (unsigned)Wo) + (unsigned)wo) << cshift) + 4 * q, acc);
+      st4(youttile + ((__umul24(__umul24(img, (unsigned)Ho) + (unsigned)ho, (unsigned)Wo) + (unsigned)wo) << cshift) + 4 * q, acc);
       acc = sub4(acc, pv);
       s1.add(acc);
       s2.addmul(acc, acc);
@@ -365,14 +365,14 @@ dw_fwd_tiled_k(const T* __restrict__ yprev, const float* __restrict__ bn_prev,
 #ifndef TTK_DW_BWD_LEAN_PIX2
 #define TTK_DW_BWD_LEAN_PIX2 4  // stride 2 (6 measured slower: 276 vs 263 us on the 65 x 65 x 64 layer)
 #endif
-template <int S, typename T, typename TG, int SL, bool LEAN, bool CARRY>
+template <int S, int SL, bool LEAN, bool CARRY>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_DW_WGS_PER_CU, TTK_DW_WGS_PER_CU)))  // <= 168 VGPRs: 3 workgroups per CU, as the LDS tile allows
-dw_bwd_tiled_k(const TG* __restrict__ g_dw, const T* __restrict__ y_dw,
+dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
                                                           const float* __restrict__ bn_dw, const float* __restrict__ w,
-                                                          const TG* __restrict__ skip_grad,
-                                                          const T* __restrict__ yprev, float* __restrict__ bn_prev,
-                                                          const T* __restrict__ skip_prev, const T* __restrict__ a_in,
-                                                          TG* __restrict__ g_prev, float* __restrict__ part,
+                                                          const float* __restrict__ skip_grad,
+                                                          const float* __restrict__ yprev, float* __restrict__ bn_prev,
+                                                          const float* __restrict__ skip_prev, const float* __restrict__ a_in,
+                                                          float* __restrict__ g_prev, float* __restrict__ part,
                                                           float* __restrict__ dwgrad, float* __restrict__ dw_partial, int B, int H, int W, int C, int Ho, int Wo,
                                                           int R, int nbands, int nslabs, int stage_floats, int NI_, int NCT_, int TW, int ring) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // dy[NI][stage_rows][Wo+2][SL] + reduction scratch
@@ -420,13 +420,13 @@ dw_bwd_tiled_k(const TG* __restrict__ g_dw, const T* __restrict__ y_dw,
     // one 64-bit base per tile and tensor, 32-bit element offsets from 24-bit multiplies (see the forward kernel)
     // channel block `slab`, first pixel of image n0 (uniform: scalar registers)
     const size_t tdy = ((size_t)slab * B * Ho * Wo + (size_t)n0 * Ho * Wo) * kCB, tin = ((size_t)slab * B * H * W + (size_t)n0 * H * W) * kCB;
-    const TG* gtile = g_dw + tdy;
-    const T* ydtile = y_dw + tdy;
-    const T* yptile = yprev + tin;
-    const T* aitile = a_in ? a_in + tin : nullptr;
-    const T* sktile = skip_prev ? skip_prev + tin : nullptr;
-    const TG* sgtile = skip_grad ? skip_grad + tin : nullptr;
-    TG* gptile = g_prev + tin;
+    const float* gtile = g_dw + tdy;
+    const float* ydtile = y_dw + tdy;
+    const float* yptile = yprev + tin;
+    const float* aitile = a_in ? a_in + tin : nullptr;
+    const float* sktile = skip_prev ? skip_prev + tin : nullptr;
+    const float* sgtile = skip_grad ? skip_grad + tin : nullptr;
+    float* gptile = g_prev + tin;
     // carry mode: dy rows ho_lo .. ho_lo + ov - 1 of this band are the last ov staged rows of the previous one.  They STAY where they are: the
     // stage is a ring of `ring` rows (dy row ho of an image lives in ring row ho mod ring), a band stages only its new rows behind them.  (The
     // forward kernel hands its shared rows over through five float4 registers; here that broke the 168-register cap of three workgroups per
@@ -460,8 +460,8 @@ dw_bwd_tiled_k(const TG* __restrict__ g_dw, const T* __restrict__ y_dw,
         }
         in[u] = ee < nstage && col >= 0 && col < Wo;
         const unsigned off = in[u] ? ((__umul24(__umul24(img, (unsigned)Ho) + (unsigned)row, (unsigned)Wo) + (unsigned)col) << cshift) + 4 * q : 0u;  // qq == q (see forward)
-        gv[u] = in[u] ? Act<TG>::ldnt(gtile + off) : f4(0.f);
-        yv[u] = in[u] ? Act<T>::ldnt(ydtile + off) : f4(0.f);
+        gv[u] = in[u] ? ld4nt(gtile + off) : f4(0.f);
+        yv[u] = in[u] ? ld4nt(ydtile + off) : f4(0.f);
       }
 #pragma unroll
       for (int u = 0; u < kBwdU; ++u) {
@@ -494,15 +494,15 @@ dw_bwd_tiled_k(const TG* __restrict__ g_dw, const T* __restrict__ y_dw,
         offs[j] = ((__umul24(__umul24(imgs[j], (unsigned)H) + (unsigned)his[j], (unsigned)W) + (unsigned)wis[j]) << cshift) + 4 * q;
       }
 #pragma unroll
-      for (int j = 0; j < NP; ++j) yps[j] = Act<T>::ldnt(yptile + offs[j]);
+      for (int j = 0; j < NP; ++j) yps[j] = ld4nt(yptile + offs[j]);
 #pragma unroll
       for (int j = 0; j < NP; ++j) {
         raws[j] = f4(0.f);
         sgs[j] = f4(0.f);
         if (!LEAN) {
-          if (a_in) raws[j] = Act<T>::ldnt(aitile + offs[j]);
-          else if (skip_prev) raws[j] = Act<T>::ldnt(sktile + offs[j]);
-          if (skip_grad) sgs[j] = Act<TG>::ldnt(sgtile + offs[j]);
+          if (a_in) raws[j] = ld4nt(aitile + offs[j]);
+          else if (skip_prev) raws[j] = ld4nt(sktile + offs[j]);
+          if (skip_grad) sgs[j] = ld4nt(sgtile + offs[j]);
         }
       }
 #pragma unroll
@@ -534,8 +534,8 @@ dw_bwd_tiled_k(const TG* __restrict__ g_dw, const T* __restrict__ y_dw,
           }
         }
         if (!LEAN && skip_grad) G = add4(G, sg);
-        const float4 gp = Act<TG>::round(mask4(G, a));  // sums and maximum of what is stored
-        Act<TG>::st(gptile + offs[j], gp);
+        const float4 gp = mask4(G, a);
+        st4(gptile + offs[j], gp);
         gmx = fmaxf(fmaxf(gmx, fmaxf(fabsf(gp.x), fabsf(gp.y))), fmaxf(fabsf(gp.z), fabsf(gp.w)));
         s1.add(gp);
         s2.addmul(gp, sub4(yp, bnp.mean));
@@ -574,6 +574,13 @@ __global__ void zero_fill_k(float* p, int64_t n) {
   if (i < n) p[i] = 0.f;
 }
 
+// a run-time flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+static void with_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 static bool dw_shape_ok2(int B, int H, int W, int C, int stride) {
   return B > 0 && H > 0 && W > 0 && W <= 256 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0 && (stride == 1 || stride == 2);
 }
@@ -589,34 +596,38 @@ int ttk_partial_rows_dwconv(int B, int H, int W, int C, int stride, int backward
   return dw_tiling(B, H, W, C, stride, backward != 0).rows;
 }
 
-int ttk_dwconv3x3_fwd(const void* yprev, const float* bn_prev, const void* skip_prev, void* a_out, const float* w, void* y,
+int ttk_dwconv3x3_fwd(const float* yprev, const float* bn_prev, const float* skip_prev, float* a_out, const float* w, float* y,
                       float* part, const float* pivot, int B, int H, int W, int C, int stride, int act_bf16, ttk_stream_t stream) {
   TTK_REQUIRE(yprev && bn_prev && w && y, "dwconv3x3_fwd: null pointer");
   TTK_REQUIRE(dw_shape_ok2(B, H, W, C, stride), "dwconv3x3_fwd: unsupported shape B=%d H=%d W=%d C=%d stride=%d (C: power of two in 32..1024, W <= 256)", B, H, W, C, stride);
   TTK_REQUIRE(!(a_out && stride != 1), "dwconv3x3_fwd: a_out requires stride 1");
+  TTK_REQUIRE_FP32_STORAGE(act_bf16, "dwconv3x3_fwd");
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const DwTiling t = dw_tiling(B, H, W, C, stride, false);
   TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "dwconv3x3_fwd: too many tiles for 32-bit indexing");
   const size_t stage = (size_t)t.NI * t.stage_rows * ((t.NCT > 1 ? t.TW : W) + 2) * t.SL;
   const size_t sm = (stage + 16 * t.SL) * sizeof(float);  // + [4][2][SL] doubles of reduction scratch
-#define TTK_DW_FWD_SL(S_, SK_, SL_, CY_)                                                                                                     \
-  hipLaunchKernelGGL((dw_fwd_tiled_k<S_, ActT, SK_, SL_, CY_>), dim3(t.grid), dim3(kBlock), sm, (hipStream_t)stream, (const ActT*)yprev, bn_prev, \
-                     (const ActT*)skip_prev, (ActT*)a_out, w, (ActT*)y, part, pivot, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, t.NI, t.NCT, t.TW)
-#define TTK_DW_FWD(S_, SK_) do { if (t.carry) TTK_DW_FWD_SL(S_, SK_, kCB, true); else TTK_DW_FWD_SL(S_, SK_, kCB, false); } while (0)
-  TTK_ACT_DISPATCH(act_bf16, if (stride == 1) { if (skip_prev) TTK_DW_FWD(1, true); else TTK_DW_FWD(1, false); }
-                             else { if (skip_prev) TTK_DW_FWD(2, true); else TTK_DW_FWD(2, false); });
-#undef TTK_DW_FWD
-#undef TTK_DW_FWD_SL
+  // the specialisation <stride 1 | 2, residual input, slab = kCB, carry mode>
+  with_flag(stride == 2, [&](auto s2) {
+    with_flag(skip_prev != nullptr, [&](auto skip) {
+      with_flag(t.carry != 0, [&](auto carry) {
+        hipLaunchKernelGGL((dw_fwd_tiled_k<decltype(s2)::value ? 2 : 1, decltype(skip)::value, kCB, decltype(carry)::value>), dim3(t.grid), dim3(kBlock), sm,
+                           (hipStream_t)stream, yprev, bn_prev, skip_prev, a_out, w, y, part, pivot, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, t.NI,
+                           t.NCT, t.TW);
+      });
+    });
+  });
   TTK_LAUNCH_CHECK("dwconv3x3_fwd");
 }
 
-int ttk_dwconv3x3_bwd_data(const void* g_dw, const void* y_dw, const float* bn_dw, const float* w, const void* skip_grad,
-                           const void* yprev, float* bn_prev, const void* skip_prev, const void* a_in, void* g_prev,
+int ttk_dwconv3x3_bwd_data(const float* g_dw, const float* y_dw, const float* bn_dw, const float* w, const float* skip_grad,
+                           const float* yprev, float* bn_prev, const float* skip_prev, const float* a_in, float* g_prev,
                            float* part, float* dw, int dw_accumulate, float* dw_partial, int B, int H, int W, int C, int stride,
                            int act_bf16, ttk_stream_t stream) {
   TTK_REQUIRE(g_dw && y_dw && bn_dw && w && yprev && bn_prev && g_prev, "dwconv3x3_bwd_data: null pointer");
   TTK_REQUIRE(dw_shape_ok2(B, H, W, C, stride), "dwconv3x3_bwd_data: unsupported shape");
   TTK_REQUIRE(!(skip_grad && stride != 1), "dwconv3x3_bwd_data: residual gradient requires stride 1");
+  TTK_REQUIRE_FP32_STORAGE(act_bf16, "dwconv3x3_bwd_data");
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const DwTiling t = dw_tiling(B, H, W, C, stride, true);
   TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "dwconv3x3_bwd_data: too many tiles for 32-bit indexing");
@@ -626,20 +637,16 @@ int ttk_dwconv3x3_bwd_data(const void* g_dw, const void* y_dw, const float* bn_d
   if (!dw) dw_partial = nullptr;
   TTK_REQUIRE(dw_accumulate != 2 || dw_partial, "dwconv3x3_bwd_data: dw_accumulate = 2 (rows folded by the caller) needs dw and dw_partial");
   if (dw && !dw_accumulate && !dw_partial) hipLaunchKernelGGL(zero_fill_k, dim3((9 * C + 255) / 256), dim3(256), 0, st, dw, (int64_t)9 * C);
-#define TTK_DW_BWD(S_) TTK_DW_BWD_SL(S_, kCB)
-#define TTK_DW_BWD_SL(S_, SL_) \
-  TTK_DW_BWD_C(S_, SL_, true); else TTK_DW_BWD_C(S_, SL_, false)
-#define TTK_DW_BWD_C(S_, SL_, LEAN_) do { if (t.carry) TTK_DW_BWD_L(S_, SL_, LEAN_, true); else TTK_DW_BWD_L(S_, SL_, LEAN_, false); } while (0)
-#define TTK_DW_BWD_L(S_, SL_, LEAN_, CY_)                                                                                                 \
-  hipLaunchKernelGGL((dw_bwd_tiled_k<S_, ActT, GradT, SL_, LEAN_, CY_>), dim3(t.grid), dim3(kBlock), sm, st, (const GradT*)g_dw, (const ActT*)y_dw, bn_dw, w, \
-                     (const GradT*)skip_grad, (const ActT*)yprev, bn_prev, (const ActT*)skip_prev, (const ActT*)a_in, (GradT*)g_prev, part,  \
-                     dw, dw_partial, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, (int)stage, t.NI, t.NCT, t.TW, t.stage_rows)
-  const bool lean = !a_in && !skip_prev && !skip_grad;
-  TTK_ACT_DISPATCH(act_bf16, if (stride == 1) { if (lean) TTK_DW_BWD(1); } else { if (lean) TTK_DW_BWD(2); });
-#undef TTK_DW_BWD_L
-#undef TTK_DW_BWD_C
-#undef TTK_DW_BWD
-#undef TTK_DW_BWD_SL
+  // the specialisation <stride 1 | 2, slab = kCB, no residual operands, carry mode>
+  with_flag(stride == 2, [&](auto s2) {
+    with_flag(!a_in && !skip_prev && !skip_grad, [&](auto lean) {
+      with_flag(t.carry != 0, [&](auto carry) {
+        hipLaunchKernelGGL((dw_bwd_tiled_k<decltype(s2)::value ? 2 : 1, kCB, decltype(lean)::value, decltype(carry)::value>), dim3(t.grid), dim3(kBlock), sm, st,
+                           g_dw, y_dw, bn_dw, w, skip_grad, yprev, bn_prev, skip_prev, a_in, g_prev, part, dw, dw_partial, B, H, W, C, Ho, Wo, t.R,
+                           t.nbands, t.nslabs, (int)stage, t.NI, t.NCT, t.TW, t.stage_rows);
+      });
+    });
+  });
   // dw_accumulate == 2: the rows stay unfolded - the caller folds them beside the BatchNorm-backward finalisation (ttk_bc_bn_bwd_finalize_fold)
   if (dw_partial && dw_accumulate != 2) launch_fold_partials(dw_partial, t.rows, (int64_t)9 * C, dw, dw_accumulate, st);
   TTK_LAUNCH_CHECK("dwconv3x3_bwd_data");

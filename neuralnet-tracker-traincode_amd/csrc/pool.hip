@@ -1,6 +1,7 @@
 // Global average pooling over the last block's output (AdaptiveAvgPool2d(1) + view,
 // backbones/mobilenet_v1.py:143,180-181) with the last BatchNorm+residual+ReLU applied on load, and
-// its backward, which starts the chain of BatchNorm-backward partial sums.
+// its backward, which starts the chain of BatchNorm-backward partial sums.  float32 tensors (the flag argument carries the LAYOUT bits
+// only; its storage bits must be 0: ttk.h).
 #include "ttk_common.h"
 
 namespace ttk {
@@ -14,9 +15,8 @@ __device__ __forceinline__ size_t pool_off(int layout, int64_t m, int c, int64_t
 }
 
 // thread = (sample, channel quad)
-template <typename T>
-__global__ void __launch_bounds__(kBlock) avgpool_fwd_k(const T* __restrict__ y, const float* __restrict__ bnp,
-                                                         const T* __restrict__ skip,
+__global__ void __launch_bounds__(kBlock) avgpool_fwd_k(const float* __restrict__ y, const float* __restrict__ bnp,
+                                                         const float* __restrict__ skip,
                                                          float* __restrict__ feat, int B, int HW, int C, int rows_layout) {
   const int quads = C >> 2;
   const int64_t items = (int64_t)B * quads;
@@ -29,16 +29,15 @@ __global__ void __launch_bounds__(kBlock) avgpool_fwd_k(const T* __restrict__ y,
     for (int p = 0; p < HW; ++p) {
       const int64_t m = (int64_t)n * HW + p;
       const size_t off = pool_off(rows_layout, m, 4 * c4, (int64_t)B * HW, C);
-      s = add4(s, skip ? bn.act(Act<T>::ld(y + off), Act<T>::ld(skip + off)) : bn.act(Act<T>::ld(y + off)));
+      s = add4(s, skip ? bn.act(ld4(y + off), ld4(skip + off)) : bn.act(ld4(y + off)));
     }
     st4(feat + (size_t)n * C + 4 * c4, make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv));
   }
 }
 
 // thread = (sample, pixel, channel quad)
-template <typename T, typename TG>
-__global__ void __launch_bounds__(kBlock) avgpool_bwd_k(const float* __restrict__ gfeat, const T* __restrict__ y,
-                                                         float* __restrict__ bnp, const T* __restrict__ skip, TG* __restrict__ g,
+__global__ void __launch_bounds__(kBlock) avgpool_bwd_k(const float* __restrict__ gfeat, const float* __restrict__ y,
+                                                         float* __restrict__ bnp, const float* __restrict__ skip, float* __restrict__ g,
                                                          float* __restrict__ part, int B, int HW, int C, int qshift, int rows_layout) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int quads = C >> 2;
@@ -51,11 +50,11 @@ __global__ void __launch_bounds__(kBlock) avgpool_bwd_k(const float* __restrict_
   for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < items; idx += (int64_t)gridDim.x * kBlock) {
     const int n = (int)((unsigned)(idx >> qshift) / (unsigned)HW);  // 32-bit division (the host checks that B * HW fits)
     const size_t off = pool_off(rows_layout, idx >> qshift, 4 * c4, (int64_t)B * HW, C);
-    const float4 yv = Act<T>::ld(y + off);
-    const float4 a = skip ? bn.act(yv, Act<T>::ld(skip + off)) : bn.act(yv);
+    const float4 yv = ld4(y + off);
+    const float4 a = skip ? bn.act(yv, ld4(skip + off)) : bn.act(yv);
     float4 gv = ld4(gfeat + (size_t)n * C + 4 * c4);
-    gv = Act<TG>::round(mask4(make_float4(gv.x * inv, gv.y * inv, gv.z * inv, gv.w * inv), a));  // sums / maximum of what is stored
-    Act<TG>::st(g + off, gv);
+    gv = mask4(make_float4(gv.x * inv, gv.y * inv, gv.z * inv, gv.w * inv), a);
+    st4(g + off, gv);
     gmx = fmaxf(fmaxf(gmx, fmaxf(fabsf(gv.x), fabsf(gv.y))), fmaxf(fabsf(gv.z), fabsf(gv.w)));
     s1 = add4(s1, gv);
     s2 = fma4(gv, sub4(yv, bn.mean), s2);
@@ -73,6 +72,9 @@ __global__ void __launch_bounds__(kBlock) avgpool_bwd_k(const float* __restrict_
 
 using namespace ttk;
 
+// the layout bits of the storage / layout flag (ttk.h) as the kernels' layout argument (pool_off)
+static int pool_layout(int flags) { return (flags & TTK_LAYOUT_ROWS) ? 1 : ((flags & TTK_LAYOUT_CB64) ? 2 : 0); }
+
 static int log2i_(int v) {
   int r = 0;
   while ((1 << r) < v) ++r;
@@ -81,25 +83,27 @@ static int log2i_(int v) {
 
 extern "C" {
 
-int ttk_avgpool_fwd(const void* y, const float* bn, const void* skip, float* feat, int B, int HW,
+int ttk_avgpool_fwd(const float* y, const float* bn, const float* skip, float* feat, int B, int HW,
                     int C, int act_bf16, ttk_stream_t stream) {
   TTK_REQUIRE(y && bn && feat, "avgpool_fwd: null pointer");
   TTK_REQUIRE(B > 0 && HW > 0 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0, "avgpool_fwd: unsupported shape B=%d HW=%d C=%d", B, HW, C);
+  TTK_REQUIRE_FP32_STORAGE(act_bf16, "avgpool_fwd");
   const int64_t items = (int64_t)B * (C / 4);
-  TTK_ACT_DISPATCH(act_bf16, hipLaunchKernelGGL((avgpool_fwd_k<ActT>), dim3(elementwise_grid(items)), dim3(kBlock), 0, (hipStream_t)stream,
-                                                (const ActT*)y, bn, (const ActT*)skip, feat, B, HW, C, (act_bf16 & TTK_LAYOUT_ROWS) ? 1 : ((act_bf16 & TTK_LAYOUT_CB64) ? 2 : 0)));
+  hipLaunchKernelGGL(avgpool_fwd_k, dim3(elementwise_grid(items)), dim3(kBlock), 0, (hipStream_t)stream, y, bn, skip, feat, B, HW, C,
+                     pool_layout(act_bf16));
   TTK_LAUNCH_CHECK("avgpool_fwd");
 }
 
-int ttk_avgpool_bwd(const float* gfeat, const void* y, float* bn, const void* skip, void* g,
+int ttk_avgpool_bwd(const float* gfeat, const float* y, float* bn, const float* skip, float* g,
                     float* part, int B, int HW, int C, int act_bf16, ttk_stream_t stream) {
   TTK_REQUIRE(gfeat && y && bn && g, "avgpool_bwd: null pointer");
   TTK_REQUIRE(B > 0 && HW > 0 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0, "avgpool_bwd: unsupported shape");
   TTK_REQUIRE((int64_t)B * HW < (int64_t)1 << 31, "avgpool_bwd: too many pixels for 32-bit indexing");
+  TTK_REQUIRE_FP32_STORAGE(act_bf16, "avgpool_bwd");
   const int qs = log2i_(C / 4);
   const int64_t items = ((int64_t)B * HW) << qs;
-  TTK_ACT_DISPATCH(act_bf16, hipLaunchKernelGGL((avgpool_bwd_k<ActT, GradT>), dim3(elementwise_grid(items)), dim3(kBlock), 2 * (size_t)C * sizeof(float),
-                                                (hipStream_t)stream, gfeat, (const ActT*)y, bn, (const ActT*)skip, (GradT*)g, part, B, HW, C, qs, (act_bf16 & TTK_LAYOUT_ROWS) ? 1 : ((act_bf16 & TTK_LAYOUT_CB64) ? 2 : 0)));
+  hipLaunchKernelGGL(avgpool_bwd_k, dim3(elementwise_grid(items)), dim3(kBlock), 2 * (size_t)C * sizeof(float), (hipStream_t)stream, gfeat, y, bn,
+                     skip, g, part, B, HW, C, qs, pool_layout(act_bf16));
   TTK_LAUNCH_CHECK("avgpool_bwd");
 }
 

@@ -131,15 +131,15 @@ __device__ __forceinline__ void producer_schedule(int nks, Prefetch&& prefetch, 
 // A: fp32 rows [M][K] (formed on load: forward relu(bn(y)), data gradient ga*(g-gmean)+gb*(y-mean)), bound in
 // bnA[TTK_BN_AUX][AMODE == BNRELU ? TTK_AUX_ACT_BOUND : TTK_AUX_DY_BOUND]; Bq: two fp16 planes [K/32][Nout][32] of the
 // weights scaled by pow2_scale(*wmax).
-// T: storage of activations (A1 = y, E0 = mask operand); TO: storage of the A0 operand and of the output - activations in the
+// A1 = y and E0 = the mask operand are activations; A0 and the output are activations in the
 // forward pass, activation gradients in the data gradient
 // GATHER (conv.hip, the ResNet18 variant): implicit-GEMM convolution - the A rows are gathered per tap (conv_geom.h),
 // K = taps * geo.Kc, the BatchNorm block of the A operand has geo.Kc channels; AMODE_PLAIN: A0 is a materialised
 // activation whose bound is *a_bound; the masked epilogue raises bnE[TTK_BN_AUX][TTK_AUX_GMAX] to max |out|.
-template <int BM, int BN, int AMODE, int EMODE, int D, typename T, typename TO, bool GATHER = false>
+template <int BM, int BN, int AMODE, int EMODE, int D, bool GATHER = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM + BN <= 256 ? 4 : 2, BM + BN <= 256 ? 4 : 2)))
-pw16_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restrict__ bnA,
-       const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, TO* __restrict__ out, const T* __restrict__ E0,
+pw16_k(const float* __restrict__ A0, const float* __restrict__ A1, const float* __restrict__ bnA,
+       const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, float* __restrict__ out, const float* __restrict__ E0,
        float* __restrict__ bnE, float* __restrict__ part, int64_t M, int K, int Nout, const float* __restrict__ a_bound,
        ConvGeom geo) {
   static_assert((BM == 128 && BN == 256) || (BM == 256 && BN == 128) || (BM == 256 && BN == 64) || (BM == 128 && BN == 64), "tile shapes");
@@ -242,8 +242,8 @@ pw16_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restr
       if constexpr (!GATHER) {
 #pragma unroll
         for (int i = 0; i < AP; ++i) {
-          ra0[set][i] = ld_act4<TO>(A0 + arow[i] + (size_t)ks * act_block_stride(M));  // k32 step ks = channel block ks
-          if constexpr (AMODE == AMODE_BNGRAD) ra1[set][i] = ld_act4<T>(A1 + arow[i] + (size_t)ks * act_block_stride(M));
+          ra0[set][i] = ld_act4(A0 + arow[i] + (size_t)ks * act_block_stride(M));  // k32 step ks = channel block ks
+          if constexpr (AMODE == AMODE_BNGRAD) ra1[set][i] = ld_act4(A1 + arow[i] + (size_t)ks * act_block_stride(M));
         }
       } else {  // the taps re-read their neighbours' rows: cached loads
         const int kh = tap / geo.KW, kw = tap - kh * geo.KW;
@@ -388,7 +388,7 @@ pw16_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restr
 #pragma unroll
     for (int i = 0; i < EI; ++i) {
       const int64_t grow = m0 + half * 128 + rr + RGH * i;
-      e0[i] = grow < M ? Act<T>::ld(E0 + (GATHER ? (size_t)grow * Nout + col : act_off(grow, col, M))) : f4(0.f);
+      e0[i] = grow < M ? ld4(E0 + (GATHER ? (size_t)grow * Nout + col : act_off(grow, col, M))) : f4(0.f);
     }
   }
   __syncthreads();
@@ -416,17 +416,16 @@ pw16_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restr
       o = ((size_t)(n * geo.Hg + 2 * ch + ph) * geo.Wg + 2 * cw + pw) * Nout + col;
     }
     if constexpr (EMODE == EMODE_PLAIN) {
-      Act<TO>::st(out + o, Act<TO>::round(v));
+      st4(out + o, v);
     } else if constexpr (EMODE == EMODE_STATS) {
-      v = Act<TO>::round(v);  // statistics of what is stored
-      Act<TO>::st(out + o, v);
+      st4(out + o, v);
       v = sub4(v, emean);
       s1 = add4(s1, v);
       s2 = fma4(v, v, s2);
     } else {
       const float4 yc = sub4(e0[i], emean);
-      v = Act<TO>::round(mask4(v, fma4(esc, yc, ebeta)));
-      Act<TO>::st(out + o, v);
+      v = mask4(v, fma4(esc, yc, ebeta));
+      st4(out + o, v);
       s1 = add4(s1, v);
       s2 = fma4(v, yc, s2);
       if constexpr (GATHER) vmx = fmaxf(vmx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
@@ -470,10 +469,10 @@ pw16_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restr
 // half the A bytes through the L1 and no BatchNorm arithmetic here); Y is not read.
 // APLANES: G / Y are the h / l fp16 planes [M][Cout] of dy * pow2_scale(bound) (ttk_bn_bwd_apply): the A producers only
 // transpose 16-bit values (v_perm) - no loads of y, no BatchNorm arithmetic, no conversion.
-template <int BM, int BN, int D, typename T, typename TG, bool CONV = false, bool APLAIN = false, bool APLANES = false>
+template <int BM, int BN, int D, bool CONV = false, bool APLAIN = false, bool APLANES = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(CONV && BM + BN <= 256 ? 4 : 2, CONV && BM + BN <= 256 ? 4 : 2)))
-pw16_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __restrict__ bn_pw,
-             const T* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ dW, float* __restrict__ partial,
+pw16_wgrad_k(const float* __restrict__ G, const float* __restrict__ Y, const float* __restrict__ bn_pw,
+             const float* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ dW, float* __restrict__ partial,
              int64_t M, int Cin, int Cout, int64_t rows_per_slice, const float* __restrict__ x_bound, ConvGeom geo) {
   static_assert((BM + BN == 384 && (BM == 128 || BM == 256)) || (BM == 128 && BN == 128) || (CONV && BM == 64 && (BN == 256 || BN == 192)),
                 "128x256, 256x128, 128x128 or (convolutions) 64x256, 64x192");
@@ -562,9 +561,7 @@ pw16_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __r
     // between consecutive rows, and the offset of channel c in row 0
     const int64_t rsA = CONV ? (int64_t)Cout : kCB, rsX = CONV ? (int64_t)Kc : kCB;
     auto colo = [&](int c) -> int64_t { return CONV ? (int64_t)c : (int64_t)act_off(0, c, M); };
-    const TG* gp[AP];
-    const T* yp[AP];
-    const T* xp[BP];
+    const float *gp[AP], *yp[AP], *xp[BP];
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
       gp[p] = G + (m_begin + 4 * mb) * rsA + colo(ca[p]);
@@ -611,8 +608,8 @@ pw16_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __r
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int p = 0; p < AP; ++p) {
-            rg[set][p][i] = ld_act4<TG>(gp[p] + base + (int64_t)i * rsA);
-            if constexpr (!APLAIN) ry[set][p][i] = ld_act4<T>(yp[p] + base + (int64_t)i * rsA);
+            rg[set][p][i] = ld_act4(gp[p] + base + (int64_t)i * rsA);
+            if constexpr (!APLAIN) ry[set][p][i] = ld_act4(yp[p] + base + (int64_t)i * rsA);
           }
         return;
       }
@@ -622,8 +619,8 @@ pw16_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __r
         row = row < m_end ? row : m_end - 1;
 #pragma unroll
         for (int p = 0; p < AP; ++p) {
-          rg[set][p][i] = ld_act4<TG>(G + row * rsA + colo(ca[p]));
-          if constexpr (!APLAIN) ry[set][p][i] = ld_act4<T>(Y + row * rsA + colo(ca[p]));
+          rg[set][p][i] = ld_act4(G + row * rsA + colo(ca[p]));
+          if constexpr (!APLAIN) ry[set][p][i] = ld_act4(Y + row * rsA + colo(ca[p]));
         }
       }
     };
@@ -674,7 +671,7 @@ pw16_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __r
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int p = 0; p < BP; ++p) rx[set][p][i] = ld_act4<T>(xp[p] + base + (int64_t)i * rsX);
+          for (int p = 0; p < BP; ++p) rx[set][p][i] = ld_act4(xp[p] + base + (int64_t)i * rsX);
         return;
       }
       const int64_t r0 = m_begin + (int64_t)ks * 32 + 4 * mb;
@@ -683,7 +680,7 @@ pw16_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __r
         int64_t row = r0 + i;
         row = row < m_end ? row : m_end - 1;
 #pragma unroll
-        for (int p = 0; p < BP; ++p) rx[set][p][i] = ld_act4<T>(X + row * rsX + colo(cb[p]));
+        for (int p = 0; p < BP; ++p) rx[set][p][i] = ld_act4(X + row * rsX + colo(cb[p]));
       }
     };
     auto store_a = [&](int ks, auto setc) {
@@ -857,8 +854,7 @@ size_t f16_wgrad_partial_bytes(int64_t M, int Cin, int Cout) {
   return (size_t)slices * Cin * Cout * sizeof(float);
 }
 
-template <typename T, typename TG>
-bool launch_f16_wgrad(const TG* g, const T* y, const float* bn_pw, const T* ydw, const float* bn_dw, float* dw,
+bool launch_f16_wgrad(const float* g, const float* y, const float* bn_pw, const float* ydw, const float* bn_dw, float* dw,
                       float* partial, int64_t M, int Cin, int Cout, hipStream_t st) {
   if (!f16_wgrad_shape(Cin, Cout)) return false;
   const bool wide = Cin % 256 == 0;  // 128 (Cout) x 256 (Cin) tiles, else 256 x 128, else (128 x 128 channels) one 128 x 128 tile
@@ -867,11 +863,11 @@ bool launch_f16_wgrad(const TG* g, const T* y, const float* bn_pw, const T* ydw,
   wgrad_slices(M, tiles, slices, rows);
   const dim3 grid(tiles, (unsigned)slices);
   if (!wide && Cout % 256 != 0)
-    hipLaunchKernelGGL((pw16_wgrad_k<128, 128, TTK_DW, T, TG>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
+    hipLaunchKernelGGL((pw16_wgrad_k<128, 128, TTK_DW>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
   else if (wide)
-    hipLaunchKernelGGL((pw16_wgrad_k<128, 256, TTK_DW, T, TG>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
+    hipLaunchKernelGGL((pw16_wgrad_k<128, 256, TTK_DW>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
   else  // (one register set: two spill)
-    hipLaunchKernelGGL((pw16_wgrad_k<256, 128, 1, T, TG>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
+    hipLaunchKernelGGL((pw16_wgrad_k<256, 128, 1>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
   if (partial) {
     const int64_t n = (int64_t)Cin * Cout;
     hipLaunchKernelGGL(wgrad_reduce_k, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, st, partial, dw, n, (int)slices);
@@ -879,16 +875,7 @@ bool launch_f16_wgrad(const TG* g, const T* y, const float* bn_pw, const T* ydw,
   return true;
 }
 
-// ---- weight operand: |w| maximum of the layer (as ordered uint bits), then the two fp16 planes [K/32][rows][32] ----
-__global__ void __launch_bounds__(256) w16_absmax_k(const float* __restrict__ w, int64_t n, unsigned* __restrict__ wmax) {
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __hip_atomic_load(wmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMax(wmax, __float_as_uint(m));  // non-negative floats order like their bit patterns
-}
-
+// ---- weight operand: |w| maximum of the layer (w16_absmax_k, split16.h), then the two fp16 planes [K/32][rows][32] ----
 // w[rows][K] fp32 -> two fp16 planes [K/32][rows][32] of w * pow2_scale(*wmax)
 __global__ void w16_split_k(const float* __restrict__ w, uint16_t* __restrict__ q, const float* __restrict__ wmax, int rows, int K) {
   const int64_t n = (int64_t)rows * K;
@@ -906,29 +893,27 @@ __global__ void w16_split_k(const float* __restrict__ w, uint16_t* __restrict__ 
 // Returns true when the shape was handled here (and the kernels launched on `st`).  Bm != nullptr: raw weight rows
 // [Nout][K] that are split into `planes` first (per-call form, unit tests); wmax: the layer's |w| maximum (a device
 // float that the per-call form computes itself).
-template <int MODE, typename T, typename TO>
-bool launch_f16_gemm(const TO* A0, const T* A1, const float* bnA, const float* Bm, TO* out, const T* E0,
+template <int MODE>
+bool launch_f16_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0,
                      const float* bnE, float* part, int64_t M, int K, int Nout, void* planes, float* wmax, hipStream_t st) {
   constexpr int AM = MODE == SMODE_FWD ? AMODE_BNRELU : AMODE_BNGRAD, EM = MODE == SMODE_FWD ? EMODE_STATS : EMODE_MASK;
   if (!planes || !wmax || !f16_gemm_shape(K, Nout)) return false;
   uint16_t* Bq = reinterpret_cast<uint16_t*>(planes);
   const int64_t nw = (int64_t)Nout * K;
   if (Bm) {
-    (void)hipMemsetAsync(wmax, 0, sizeof(float), st);
-    hipLaunchKernelGGL(w16_absmax_k, dim3((unsigned)(nw / 1024 < 1 ? 1 : (nw / 1024 > 256 ? 256 : nw / 1024))), dim3(256), 0, st, Bm, nw,
-                       reinterpret_cast<unsigned*>(wmax));
+    launch_w16_absmax(Bm, nw, wmax, st);
     hipLaunchKernelGGL(w16_split_k, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, Bm, Bq, wmax, Nout, K);
   }
   if (Nout >= 256 && Nout % 256 == 0) {
     const unsigned tiles = (unsigned)(ceil_div(M, 128) * (Nout / 256));
-    hipLaunchKernelGGL((pw16_k<128, 256, AM, EM, TTK_D, T, TO>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
+    hipLaunchKernelGGL((pw16_k<128, 256, AM, EM, TTK_D>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
                        Nout, nullptr, ConvGeom{});
     return true;
   }
   if (Nout == 128) {
     const unsigned tiles = (unsigned)ceil_div(M, 256);
     constexpr int D = (MODE == SMODE_DGRAD || TTK_D > 2) ? 1 : TTK_D;  // eight A rows per thread: more sets spill
-    hipLaunchKernelGGL((pw16_k<256, 128, AM, EM, D, T, TO>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
+    hipLaunchKernelGGL((pw16_k<256, 128, AM, EM, D>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
                        Nout, nullptr, ConvGeom{});
     return true;
   }
@@ -971,7 +956,7 @@ bool launch_conv_wgrad16(const float* g, const float* y, const float* bn, const 
   // y == nullptr: g holds dy as two fp16 planes [M][Cout] (h, then l)
   const float* yy = y ? y : reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(g) + M * Cout);
 #define TTK_WGRAD_LAUNCH(BM_, BN_, PLAIN_)                                                                                                      \
-  hipLaunchKernelGGL((pw16_wgrad_k<BM_, BN_, (BM_ == 64 ? TTK_DC : 1), float, float, true, false, PLAIN_>), grid, dim3(512), 0, st, g, yy, bn, a_in, nullptr, dw, partial, M, ncols, \
+  hipLaunchKernelGGL((pw16_wgrad_k<BM_, BN_, (BM_ == 64 ? TTK_DC : 1), true, false, PLAIN_>), grid, dim3(512), 0, st, g, yy, bn, a_in, nullptr, dw, partial, M, ncols, \
                      Cout, rows, a_bound, geo)
   if (narrow && conv_wgrad_bn(Cout, ncols) == 192) { if (y) TTK_WGRAD_LAUNCH(64, 192, false); else TTK_WGRAD_LAUNCH(64, 192, true); }
   else if (narrow) { if (y) TTK_WGRAD_LAUNCH(64, 256, false); else TTK_WGRAD_LAUNCH(64, 256, true); }
@@ -1010,7 +995,7 @@ bool launch_conv_gemm16(int amode, int emode, const float* A0, const float* A1, 
 #define TTK_CONV_LAUNCH(BM_, BN_, AM_, EM_)                                                                                        \
   do {                                                                                                                             \
     const unsigned grid_ = grid_of(BM_, BN_);                                                                                      \
-    hipLaunchKernelGGL((pw16_k<BM_, BN_, AM_, EM_, 1, float, float, true>), dim3(grid_), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, \
+    hipLaunchKernelGGL((pw16_k<BM_, BN_, AM_, EM_, 1, true>), dim3(grid_), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, \
                        part, M, K, Nout, a_bound, gq);                                                                             \
   } while (0)
 #define TTK_CONV_TILES(AM_, EM_)                                   \
@@ -1036,14 +1021,9 @@ bool launch_conv_gemm16(int amode, int emode, const float* A0, const float* A1, 
   return false;
 }
 
-#define TTK_INST(T_, TG_)                                                                                                              \
-  template bool launch_f16_gemm<SMODE_FWD, T_, T_>(const T_*, const T_*, const float*, const float*, T_*, const T_*, const float*, float*, \
-                                                   int64_t, int, int, void*, float*, hipStream_t);                                         \
-  template bool launch_f16_gemm<SMODE_DGRAD, T_, TG_>(const TG_*, const T_*, const float*, const float*, TG_*, const T_*, const float*,    \
-                                                      float*, int64_t, int, int, void*, float*, hipStream_t);                              \
-  template bool launch_f16_wgrad<T_, TG_>(const TG_*, const T_*, const float*, const T_*, const float*, float*, float*, int64_t, int, int, \
-                                          hipStream_t);
-TTK_INST(float, float)
-#undef TTK_INST
+template bool launch_f16_gemm<SMODE_FWD>(const float*, const float*, const float*, const float*, float*, const float*, const float*, float*, int64_t,
+                                         int, int, void*, float*, hipStream_t);
+template bool launch_f16_gemm<SMODE_DGRAD>(const float*, const float*, const float*, const float*, float*, const float*, const float*, float*, int64_t,
+                                           int, int, void*, float*, hipStream_t);
 
 }  // namespace ttk

@@ -136,19 +136,11 @@ __device__ __forceinline__ unsigned rlow2(unsigned h, float x0, float x1) {
 // The producers' row loads as BUFFER loads: a wave-uniform descriptor (rebuilt per k32 step: scalar work) + one 32-bit byte offset
 // per lane.  As global loads hipcc kept a 64-bit address pair per (row pass, tensor) in registers across the loop - 24 VGPRs of the
 // data gradient's producers, which is what made a second set of rows spill.
-template <typename T>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rbuf(const T* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, 0x7fffffff, 0x00020000);
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rbuf(const float* base) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
 }
-template <typename T>
 __device__ __forceinline__ f32x4 rbuf_ld4(__amdgpu_buffer_rsrc_t r, unsigned elem_off) {  // 4 consecutive elements, streaming (nt)
-  if constexpr (Act<T>::kBf16) {
-    const u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, elem_off * 2u, 0, 2);
-    const float4 v = Act<bf16_t>::widen(make_uint2(u.x, u.y));
-    return f32x4{v.x, v.y, v.z, v.w};
-  } else {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, elem_off * 4u, 0, 2));
-  }
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, elem_off * 4u, 0, 2));
 }
 
 // Geometry of a tile of RBLK 32-row blocks x 8 32-column blocks on 8 consumer waves
@@ -170,8 +162,8 @@ struct RGeo {
 
 // ---------------- epilogue of a tile, all NW waves: the tile leaves through LDS in TM chunks of CH rows (block c of every MFMA wave) -
 // un-scale, 16-byte stores (a wave writes 1 KB row segments), the data gradient's ReLU mask, BatchNorm sums ----------------
-template <int RBLK, int MODE, int NW, typename T, typename TO, typename Acc, bool M16 = false>
-__device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, TO* __restrict__ out, const T* __restrict__ E0, const float* __restrict__ bnE,
+template <int RBLK, int MODE, int NW, typename Acc, bool M16 = false>
+__device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, float* __restrict__ out, const float* __restrict__ E0, const float* __restrict__ bnE,
                                            float* __restrict__ part, int64_t M, int Nout, int64_t m0, int64_t m_end, int n0, unsigned by, float sa, float sb) {
   using G = RGeo<RBLK>;
   constexpr int WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN;
@@ -219,7 +211,7 @@ __device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, TO* __r
         const int64_t grow = tile_row(c, cr);
         ev[idx & 1][u] = f4(0.f);
         if constexpr (!(kRDbg & 16))
-          if (cr < CH && grow < m_end) ev[idx & 1][u] = Act<T>::ld(E0 + act_off(grow, col, M));
+          if (cr < CH && grow < m_end) ev[idx & 1][u] = ld4(E0 + act_off(grow, col, M));
       }
     }
   };
@@ -256,15 +248,14 @@ __device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, TO* __r
         v = make_float4(v.x * inv, v.y * inv, v.z * inv, v.w * inv);
         const size_t o = act_off(grow, col, M);
         if constexpr (FWD) {
-          v = Act<TO>::round(v);  // statistics of what is stored
-          Act<TO>::st(out + o, v);
+          st4(out + o, v);
           v = sub4(v, emean);
           s1 = add4(s1, v);
           s2 = fma4(v, v, s2);
         } else {
           const float4 yc = sub4(ev[idx & 1][u], emean);
-          v = Act<TO>::round(mask4(v, fma4(esc, yc, ebeta)));
-          Act<TO>::st(out + o, v);
+          v = mask4(v, fma4(esc, yc, ebeta));
+          st4(out + o, v);
           s1 = add4(s1, v);
           s2 = fma4(v, yc, s2);
         }
@@ -290,10 +281,10 @@ __device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, TO* __r
 // A: fp32 rows [M][K], formed on load (forward: relu(bn(y)); data gradient: ga*(g-gmean)+gb*(y-mean)); Bq: two fp16 planes
 // [K/16][Nout][16] (chunk-swizzled) of the weights scaled by pow2_scale(*wmax).  Tile t: rows [by*RT, min((by+1)*RT, M)),
 // columns [bx*256, +256); part[by][2][Nout].
-template <int RBLK, int MODE, typename T, typename TO>
-__global__ void __launch_bounds__(768) pw16r_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restrict__ bnA,
-                                               const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, TO* __restrict__ out,
-                                               const T* __restrict__ E0, const float* __restrict__ bnE, float* __restrict__ part, int64_t M,
+template <int RBLK, int MODE>
+__global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, const float* __restrict__ A1, const float* __restrict__ bnA,
+                                               const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, float* __restrict__ out,
+                                               const float* __restrict__ E0, const float* __restrict__ bnE, float* __restrict__ part, int64_t M,
                                                int K, int Nout, int RT) {
   using G = RGeo<RBLK>;
   constexpr int RB = G::RB, WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN, APL = G::APL, BPL = G::BPL, kStr = G::kStr;
@@ -371,7 +362,7 @@ __global__ void __launch_bounds__(768) pw16r_k(const TO* __restrict__ A0, const 
       constexpr int slot = decltype(slotc)::value, hf = decltype(hfc)::value;
       // k32 step ks = channel block ks: the tile's RT x 128 contiguous bytes
       const __amdgpu_buffer_rsrc_t r0 = rbuf(A0 + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
-      const __amdgpu_buffer_rsrc_t r1 = rbuf((FWD ? (const T*)nullptr : A1) + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
+      const __amdgpu_buffer_rsrc_t r1 = rbuf((FWD ? (const float*)nullptr : A1) + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
 #pragma unroll
       for (int u = 0; u < G; ++u) {
         const int i = hf * G + u;
@@ -382,8 +373,8 @@ __global__ void __launch_bounds__(768) pw16r_k(const TO* __restrict__ A0, const 
           ra1[slot][FWD ? 0 : u] = t1;
         } else {
           const unsigned o = ((live >> i) & 1u) ? aoff0 + (unsigned)(i * 32 * kCB) : (unsigned)(kq8 * 4);  // (dead rows - pass 0's too - read row 0 of the tile)
-          ra0[slot][u] = rbuf_ld4<TO>(r0, o);
-          if constexpr (!FWD) ra1[slot][u] = rbuf_ld4<T>(r1, o);
+          ra0[slot][u] = rbuf_ld4(r0, o);
+          if constexpr (!FWD) ra1[slot][u] = rbuf_ld4(r1, o);
         }
       }
     };
@@ -579,7 +570,7 @@ __global__ void __launch_bounds__(768) pw16r_k(const TO* __restrict__ A0, const 
 #endif
   }
 #undef TTK_RB
-  r_epilogue<RBLK, MODE, 12, T, TO>(lds, acc, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
+  r_epilogue<RBLK, MODE, 12>(lds, acc, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
 #if defined(TTK_R_STAMP)
   {
     unsigned long long st_t1, st_r1;
@@ -623,10 +614,10 @@ struct MGeo {
 // reads, same cycles per flop as 32x32x16 - for two reasons: the 16-row blocks that lie wholly behind the end of the row block are
 // skipped (RT = 162 of a 192-row tile: the last of the twelve, i.e. 8 % of the matrix work), and the guide measures the 16 x 16 shape at a
 // higher clock under the power limit.  Measured: data gradient of 512 x 512 99.9 -> 97.2 us before the skip (profiles/r04_rowblock_gemm_variants.txt)
-template <int RBLK, int MODE, typename T, typename TO, bool M16>
-__global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const T* __restrict__ A1, const float* __restrict__ bnA,
-                                               const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, TO* __restrict__ out,
-                                               const T* __restrict__ E0, const float* __restrict__ bnE, float* __restrict__ part, int64_t M,
+template <int RBLK, int MODE, bool M16>
+__global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, const float* __restrict__ A1, const float* __restrict__ bnA,
+                                               const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, float* __restrict__ out,
+                                               const float* __restrict__ E0, const float* __restrict__ bnE, float* __restrict__ part, int64_t M,
                                                int K, int Nout, int RT) {
   using G = RGeo<RBLK>;
   constexpr int RB = G::RB, WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN, APL = G::APL, BPL = G::BPL, kStr = G::kStr;
@@ -681,7 +672,7 @@ __global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const 
   auto load_a = [&](int ks, auto setc) {  // rows of stage ks -> register set
     constexpr int set = decltype(setc)::value;
     const __amdgpu_buffer_rsrc_t r0 = rbuf(A0 + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
-    const __amdgpu_buffer_rsrc_t r1 = rbuf((FWD ? (const T*)nullptr : A1) + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
+    const __amdgpu_buffer_rsrc_t r1 = rbuf((FWD ? (const float*)nullptr : A1) + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
 #pragma unroll
     for (int u = 0; u < AP; ++u) {
       if constexpr (kRDbg & 1) {
@@ -691,8 +682,8 @@ __global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const 
         ra1[set][FWD ? 0 : u] = t1;
       } else {
         const unsigned o = ((live >> u) & 1u) ? aoff0 + (unsigned)(u * 64 * kCB) : (unsigned)(kq8 * 4);
-        ra0[set][u] = rbuf_ld4<TO>(r0, o);
-        if constexpr (!FWD) ra1[set][u] = rbuf_ld4<T>(r1, o);
+        ra0[set][u] = rbuf_ld4(r0, o);
+        if constexpr (!FWD) ra1[set][u] = rbuf_ld4(r1, o);
       }
     }
   };
@@ -970,8 +961,8 @@ __global__ void __launch_bounds__(512) pw16m_k(const TO* __restrict__ A0, const 
   TTK_STAMP(st_loop1);
 #endif
 #undef TTK_RB
-  if constexpr (M16) r_epilogue<RBLK, MODE, 8, T, TO, decltype(acc16), true>(lds, acc16, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
-  else r_epilogue<RBLK, MODE, 8, T, TO>(lds, acc, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
+  if constexpr (M16) r_epilogue<RBLK, MODE, 8, decltype(acc16), true>(lds, acc16, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
+  else r_epilogue<RBLK, MODE, 8>(lds, acc, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
 #if defined(TTK_R_STAMP)
   {
     unsigned long long st_t1, st_r1;
@@ -1024,9 +1015,8 @@ __device__ __forceinline__ void tsplit_store(f32x4 v, unsigned char* dst) { spli
 
 #if defined(TTK_EXPERIMENTS)  // (pw16t_wgrad_k is selectable by TTK_WGRAD_T=t only: ahead of pw16u_wgrad_k on no shape but 1024 x 1024, and there by 5 %)
 // G, Y: [M][Cout] (gradient w.r.t. the BatchNorm output, raw conv output), X: [M][Cin] (raw depthwise output); partial[slice][Cout][Cin]
-template <typename T, typename TG>
-__global__ void __launch_bounds__(768) pw16t_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __restrict__ bn_pw,
-                                                     const T* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ partial,
+__global__ void __launch_bounds__(768) pw16t_wgrad_k(const float* __restrict__ G, const float* __restrict__ Y, const float* __restrict__ bn_pw,
+                                                     const float* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ partial,
                                                      int64_t M, int Cin, int Cout, int64_t rows_per_slice) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kTRing];
   const int tid = threadIdx.x;
@@ -1065,9 +1055,9 @@ __global__ void __launch_bounds__(768) pw16t_wgrad_k(const TG* __restrict__ G, c
     auto load_row = [&](int ks, int i) {
       int64_t row = r0 + (int64_t)ks * 32 + i;
       row = row < m_end ? row : m_end - 1;  // (rows past the slice are zeroed when they are stored)
-      rg[i] = ld_act4<TG>(G + act_off(row, ca, M));
-      ry[i] = ld_act4<T>(Y + act_off(row, ca, M));
-      rx[i] = ld_act4<T>(X + act_off(row, cb, M));
+      rg[i] = ld_act4(G + act_off(row, ca, M));
+      ry[i] = ld_act4(Y + act_off(row, ca, M));
+      rx[i] = ld_act4(X + act_off(row, cb, M));
     };
     auto store = [&](int ks) {  // the eight rows of step ks: BatchNorm backward / BatchNorm + ReLU, split, to LDS
       unsigned char* dy = wdy + (ks & 1) * 2 * kTStage;
@@ -1172,9 +1162,8 @@ __global__ void __launch_bounds__(768) pw16t_wgrad_k(const TG* __restrict__ G, c
 // 8 loads (128 B) per step instead of 24, so two steps fit into registers: the loads of steps s + 1 and s + 2 are in flight while
 // step s is converted.  LDS layout, transposed fragment reads and the partial-tile + fold epilogue are those of pw16t_wgrad_k.
 // ---------------------------------------------------------------------------------------------
-template <typename T, typename TG>
-__global__ void __launch_bounds__(768) pw16u_wgrad_k(const TG* __restrict__ G, const T* __restrict__ Y, const float* __restrict__ bn_pw,
-                                                     const T* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ partial,
+__global__ void __launch_bounds__(768) pw16u_wgrad_k(const float* __restrict__ G, const float* __restrict__ Y, const float* __restrict__ bn_pw,
+                                                     const float* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ partial,
                                                      int64_t M, int Cin, int Cout, int64_t rows_per_slice) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kTRing];
   const int tid = threadIdx.x;
@@ -1220,14 +1209,14 @@ __global__ void __launch_bounds__(768) pw16u_wgrad_k(const TG* __restrict__ G, c
       for (int i = 0; i < 4; ++i) {
         int64_t row = rb + i;
         row = row < m_end ? row : m_end - 1;  // (rows past the slice are zeroed when they are stored)
-        rx[set][i] = ld_act4<T>(X + ob + (size_t)row * kCB);
+        rx[set][i] = ld_act4(X + ob + (size_t)row * kCB);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         int64_t row = rb + ra + j;
         row = row < m_end ? row : m_end - 1;
-        rg[set][j] = ld_act4<TG>(G + oa + (size_t)row * kCB);
-        ry[set][j] = ld_act4<T>(Y + oa + (size_t)row * kCB);
+        rg[set][j] = ld_act4(G + oa + (size_t)row * kCB);
+        ry[set][j] = ld_act4(Y + oa + (size_t)row * kCB);
       }
     };
     auto store = [&](int ks, auto setc) {  // BatchNorm backward / BatchNorm + ReLU, split, to LDS
@@ -1379,8 +1368,7 @@ size_t f16t_wgrad_scratch_bytes(int64_t M, int Cin, int Cout) {
   t_wgrad_plan(M, Cin, Cout, tiles, slices, rows);
   return (size_t)slices * Cin * Cout * sizeof(float);
 }
-template <typename T, typename TG>
-bool launch_f16t_wgrad(const TG* g, const T* y, const float* bn_pw, const T* ydw, const float* bn_dw, float* dw, float* partial, int64_t M,
+bool launch_f16t_wgrad(const float* g, const float* y, const float* bn_pw, const float* ydw, const float* bn_dw, float* dw, float* partial, int64_t M,
                        int Cin, int Cout, hipStream_t st) {
   if (!partial || !f16t_wgrad_shape(Cin, Cout)) return false;
   int tiles;
@@ -1388,15 +1376,14 @@ bool launch_f16t_wgrad(const TG* g, const T* y, const float* bn_pw, const T* ydw
   t_wgrad_plan(M, Cin, Cout, tiles, slices, rows);
 #if defined(TTK_EXPERIMENTS)
   if (t_wgrad_wide(Cin, Cout))
-    hipLaunchKernelGGL((pw16t_wgrad_k<T, TG>), dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
+    hipLaunchKernelGGL(pw16t_wgrad_k, dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
   else
 #endif
-    hipLaunchKernelGGL((pw16u_wgrad_k<T, TG>), dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
+    hipLaunchKernelGGL(pw16u_wgrad_k, dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
   const int64_t n = (int64_t)Cin * Cout;
   hipLaunchKernelGGL(wgrad_fold_k, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, st, partial, dw, n, (int)slices);
   return true;
 }
-template bool launch_f16t_wgrad<float, float>(const float*, const float*, const float*, const float*, const float*, float*, float*, int64_t, int, int, hipStream_t);
 
 // ---- tiling: row blocks of RT rows such that the tiles fill whole rounds of the CUs ------------------------------------------
 bool f16r_enabled() {
@@ -1461,35 +1448,25 @@ __global__ void w16r_split_k(const float* __restrict__ w, uint16_t* __restrict__
   q[o] = h;
   q[n + o] = l;
 }
-__global__ void __launch_bounds__(256) w16r_absmax_k(const float* __restrict__ w, int64_t n, unsigned* __restrict__ wmax) {
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __hip_atomic_load(wmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMax(wmax, __float_as_uint(m));
-}
 
 // Returns true when the shape was handled here (kernels launched on `st`).  Bm != nullptr: raw weight rows [Nout][K] that are split
 // into `planes` first (per-call form, unit tests); wmax: the layer's |w| maximum (a device float the per-call form computes itself).
-template <int MODE, typename T, typename TO>
-bool launch_f16r_gemm(const TO* A0, const T* A1, const float* bnA, const float* Bm, TO* out, const T* E0, const float* bnE, float* part,
+template <int MODE>
+bool launch_f16r_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0, const float* bnE, float* part,
                       int64_t M, int K, int Nout, void* planes, float* wmax, hipStream_t st) {
   if (!planes || !wmax || !f16r_gemm_shape(K, Nout, MODE == RMODE_DGRAD)) return false;
   uint16_t* Bq = reinterpret_cast<uint16_t*>(planes);
   const int64_t nw = (int64_t)Nout * K;
   if (Bm) {
-    (void)hipMemsetAsync(wmax, 0, sizeof(float), st);
-    hipLaunchKernelGGL(w16r_absmax_k, dim3((unsigned)(nw / 1024 < 1 ? 1 : (nw / 1024 > 256 ? 256 : nw / 1024))), dim3(256), 0, st, Bm, nw,
-                       reinterpret_cast<unsigned*>(wmax));
+    launch_w16_absmax(Bm, nw, wmax, st);
     hipLaunchKernelGGL(w16r_split_k, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, Bm, Bq, wmax, Nout, K);
   }
   const RPlan pl = r_plan(M, K, Nout);
   const unsigned tiles = (unsigned)pl.row_blocks * (Nout / kRBN);
 #define TTK_M_LAUNCH(RBLK_) \
-  hipLaunchKernelGGL((pw16m_k<RBLK_, MODE, T, TO, (TTK_M_M16 != 0)>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
+  hipLaunchKernelGGL((pw16m_k<RBLK_, MODE, (TTK_M_M16 != 0)>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
 #define TTK_R_LAUNCH(RBLK_) \
-  hipLaunchKernelGGL((pw16r_k<RBLK_, MODE, T, TO>), dim3(tiles), dim3(768), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
+  hipLaunchKernelGGL((pw16r_k<RBLK_, MODE>), dim3(tiles), dim3(768), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
   // Which form runs what, from same-box runs of the whole step (profiles/r04_rowblock_gemm_variants.txt): the eight-wave form takes the
   // data gradient (two tensors to convert per element: 0.617 vs 0.644 ms per step), the twelve-wave form keeps the forward (0.478 vs
   // 0.485) and the 256-row tiles (128 accumulator registers + two sets of rows do not fit the eight-wave form's 256).
@@ -1504,13 +1481,10 @@ bool launch_f16r_gemm(const TO* A0, const T* A1, const float* bnA, const float* 
   return true;
 }
 
-#define TTK_RINST(T_, TG_)                                                                                                                \
-  template bool launch_f16r_gemm<RMODE_FWD, T_, T_>(const T_*, const T_*, const float*, const float*, T_*, const T_*, const float*, float*, \
-                                                    int64_t, int, int, void*, float*, hipStream_t);                                         \
-  template bool launch_f16r_gemm<RMODE_DGRAD, T_, TG_>(const TG_*, const T_*, const float*, const float*, TG_*, const T_*, const float*,    \
-                                                       float*, int64_t, int, int, void*, float*, hipStream_t);
-TTK_RINST(float, float)
-#undef TTK_RINST
+template bool launch_f16r_gemm<RMODE_FWD>(const float*, const float*, const float*, const float*, float*, const float*, const float*, float*, int64_t,
+                                          int, int, void*, float*, hipStream_t);
+template bool launch_f16r_gemm<RMODE_DGRAD>(const float*, const float*, const float*, const float*, float*, const float*, const float*, float*, int64_t,
+                                            int, int, void*, float*, hipStream_t);
 
 }  // namespace ttk
 

@@ -81,15 +81,33 @@ __device__ __forceinline__ void split_store16(f32x4 v, unsigned char* dst, int p
   *reinterpret_cast<uint2*>(dst + plane) = l;
 }
 
+// *wmax = max |w| of a weight tensor of n elements: the bound its pieces are scaled by (pow2_scale).  Raised as ordered uint bits
+// (non-negative floats order like their bit patterns) from zero.  One kernel for every per-call weight split: pwconv_f16.hip,
+// pwconv_r.hip, ttk_conv_weight_repack.
+template <int kDummy = 0>
+__global__ void __launch_bounds__(256) w16_absmax_k(const float* __restrict__ w, int64_t n, unsigned* __restrict__ wmax) {
+  float m = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __hip_atomic_load(wmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    atomicMax(wmax, __float_as_uint(m));
+}
+template <int kDummy = 0>  // (a template so that only the files that launch it hold a copy of the kernel)
+void launch_w16_absmax(const float* w, int64_t n, float* wmax, hipStream_t st) {
+  (void)hipMemsetAsync(wmax, 0, sizeof(float), st);
+  hipLaunchKernelGGL(w16_absmax_k<kDummy>, dim3((unsigned)(n / 1024 < 1 ? 1 : (n / 1024 > 256 ? 256 : n / 1024))), dim3(256), 0, st, w, n,
+                     reinterpret_cast<unsigned*>(wmax));
+}
+
 // Byte offset of 16-byte chunk `chunk` (0 / 1) of row `row` inside the LDS image of one piece plane of a k16 stage (32 B per row): the two
 // chunks are swapped where (row >> 3) & 1, which spreads a wave's ds_read_b128 fragment reads over all banks (r_plane_index, conv_geom.h,
 // is the same order in elements)
 __device__ __forceinline__ int swz16(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 3) & 1)) << 4); }
 
 // 4 consecutive activation values as f32x4 (streamed: non-temporal)
-template <typename T>
-__device__ __forceinline__ f32x4 ld_act4(const T* p) {
-  const float4 v = Act<T>::ldnt(p);
+__device__ __forceinline__ f32x4 ld_act4(const float* p) {
+  const float4 v = ld4nt(p);
   return f32x4{v.x, v.y, v.z, v.w};
 }
 

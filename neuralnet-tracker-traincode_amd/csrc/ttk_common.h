@@ -144,10 +144,11 @@ __device__ __forceinline__ float4 sub4(float4 a, float4 b) {
   return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
 }
 
-// ---- storage type of the activation tensors that cross HBM ------------------------------------------------------
-// float (the reference's precision) for the fp32 kernel family; Act<bf16_t> (values rounded to nearest-even bf16 on their way out,
-// widened on load) is what remains of rounds 2-5's bf16 STORAGE variant: only the stem of the bf16-compute path instantiates it
-// (TTK_ACT_DISPATCH_STEM below).  Offsets are in elements either way.
+// ---- bf16 storage of activation tensors that cross HBM ------------------------------------------------------------
+// The fp32 kernel family reads and writes plain float (ld4 / ld4nt / st4 above).  Act<T> is the storage axis of the STEM pair only
+// (stem.hip, TTK_ACT_DISPATCH_STEM below): Act<float> for the fp32 path, Act<bf16_t> (values rounded to nearest-even bf16 on their way
+// out, widened on load) for the bf16-compute path, whose own kernels (csrc/bc_*.hip) share the bf16_t typedef.  Offsets are in elements
+// either way.
 typedef uint16_t bf16_t;  // storage only
 typedef __bf16 ttk_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float ttk_f32x2 __attribute__((ext_vector_type(2)));
@@ -188,13 +189,10 @@ template <> struct Act<bf16_t> {
 };
 // The storage flag of the C-ABI (TTK_STORE_* in ttk.h).  Round 6 retired the bf16 STORAGE variants of the fp32 kernels (`--precision bf16 | bf16-all`:
 // slower than fp32, superseded by the bf16-compute path's own kernels, csrc/bc_*.hip): the depthwise / pointwise / pooling entry points take fp32
-// tensors only and refuse the bits; the stem pair, which also serves the bf16-compute path (C = 32: the same bytes in either layout), takes fp32 or
-// BOTH bits (activations and gradients bfloat16).
-#define TTK_ACT_DISPATCH(flag, ...)                                                                                                             \
-  do {                                                                                                                                          \
-    TTK_REQUIRE(((flag) & 3) == 0, "bf16 activation storage under the fp32 kernels was retired (round 6): use the bf16-compute path (ttk_bc_*)"); \
-    using ActT [[maybe_unused]] = float; using GradT [[maybe_unused]] = float; __VA_ARGS__;                                         \
-  } while (0)
+// tensors only and refuse the bits with their argument checks, before anything is launched (TTK_REQUIRE_FP32_STORAGE); the stem pair, which also
+// serves the bf16-compute path (C = 32: the same bytes in either layout), takes fp32 or BOTH bits (activations and gradients bfloat16).
+#define TTK_REQUIRE_FP32_STORAGE(flag, name) \
+  TTK_REQUIRE(((flag) & 3) == 0, name ": bf16 activation storage under the fp32 kernels was retired (round 6): use the bf16-compute path (ttk_bc_*)")
 #define TTK_ACT_DISPATCH_STEM(flag, ...)                                                                                                        \
   do {                                                                                                                                          \
     TTK_REQUIRE(((flag) & 3) == 0 || ((flag) & 3) == 3, "the stem takes fp32 tensors or activations AND gradients bfloat16 (bf16-compute path)"); \
