@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 31
+#define TTK_ABI_VERSION 32
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -198,6 +198,22 @@ int ttk_dwconv3x3_bwd_data(const float* g_dw, const float* y_dw, const float* bn
                            const float* skip_prev, const float* a_in, float* g_prev, float* part,
                            float* dw, int dw_accumulate, float* dw_partial, int B, int H, int W, int C,
                            int stride, int act_bf16, ttk_stream_t stream);
+/* The RAW residual operand (ABI 32).  The residual input of a block may be given in two forms: as the stored activation x (skip_prev of the two
+ * entry points above, skip of ttk_avgpool_*), or - the four *_rawskip entry points - as the raw convolution output s that produced it together with
+ * that convolution's BatchNorm block: x = max(scale*(s - mean) + beta, 0) with skip_bn's rows, formed on load by the same arithmetic that
+ * ttk_bn_act / a_out would have stored, so every output is bit for bit that of the stored form.  The host uses it behind the FIRST block of a
+ * chain of residual blocks, whose output is its producer's relu(bn(y)) with no residual of its own: that block's input is then not stored at all
+ * (backbones/mobilenet_v1.py, _ELIDE_HEAD_INPUT).  skip_raw and skip_bn must not be NULL; everything else is the contract of the entry point
+ * without the suffix (ttk_dwconv3x3_bwd_data_rawskip has no a_in: the block input is always recomputed).  Being new, the four carry no
+ * storage / layout argument: float32 tensors in channel blocks of 32. */
+int ttk_dwconv3x3_fwd_rawskip(const float* yprev, const float* bn_prev, const float* skip_raw, const float* skip_bn, float* a_out,
+                              const float* w, float* y, float* part, const float* pivot, int B, int H, int W, int C,
+                              int stride, ttk_stream_t stream);
+int ttk_dwconv3x3_bwd_data_rawskip(const float* g_dw, const float* y_dw, const float* bn_dw, const float* w,
+                                   const float* skip_grad, const float* yprev, float* bn_prev,
+                                   const float* skip_raw, const float* skip_bn, float* g_prev, float* part,
+                                   float* dw, int dw_accumulate, float* dw_partial, int B, int H, int W, int C,
+                                   int stride, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pointwise 1x1 conv = GEMM on the matrix cores - DepthWiseBlock.conv_sep, mobilenet_v1.py:67,82.
@@ -262,6 +278,11 @@ int ttk_avgpool_fwd(const float* y, const float* bn, const float* skip, float* f
  * bn[TTK_BN_AUX][TTK_AUX_GMAX] to max |g|. */
 int ttk_avgpool_bwd(const float* gfeat, const float* y, float* bn, const float* skip, float* g,
                     float* part, int B, int HW, int C, int act_bf16, ttk_stream_t stream);
+/* ... with the residual operand given raw (see ttk_dwconv3x3_fwd_rawskip): skip = max(skip_bn(skip_raw), 0) on load. */
+int ttk_avgpool_fwd_rawskip(const float* y, const float* bn, const float* skip_raw, const float* skip_bn, float* feat, int B, int HW,
+                            int C, ttk_stream_t stream);
+int ttk_avgpool_bwd_rawskip(const float* gfeat, const float* y, float* bn, const float* skip_raw, const float* skip_bn, float* g,
+                            float* part, int B, int HW, int C, ttk_stream_t stream);
 /* a[rows][C] = max(bn(y) (+ skip), 0): materialises a post-activation tensor (the `intermediates` list
  * MobileNet.forward returns, mobilenet_v1.py:165-186).  y, skip: channel blocks; a: plain channels-last rows. */
 int ttk_bn_act(const float* y, const float* bn, const float* skip, float* a, int64_t rows, int C,

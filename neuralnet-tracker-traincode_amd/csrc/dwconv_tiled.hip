@@ -219,13 +219,23 @@ __device__ __forceinline__ void slab_partials(D4 s1, D4 s2, int q, int C, int c_
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-template <int S, bool SKIP, int SL, bool CARRY>
+// The residual operand of the block input, a_in = relu(bn(y_prev) + x): none, the STORED activation x, or - kSkipRaw - the RAW convolution
+// output s that produced x together with its BatchNorm constant block, x = relu(bn_skip(s)), formed on load with the same BnApply4::act that
+// wrote the stored tensor (bit for bit the same x).  The raw form serves the layer behind the first block of a residual chain where that
+// block does not store its input x = relu(bn(y)) (backbones/mobilenet_v1.py, _ELIDE_HEAD_INPUT).  The constant block travels
+// as ONE trailing kernel argument, `const float* bn_skip`, that only the raw instantiations have (a parameter pack of zero or one
+// pointers): the kernels of the other forms keep their argument list, and with it their generated code, as they were.
+enum { kSkipNone = 0, kSkipStored = 1, kSkipRaw = 2 };
+__device__ __forceinline__ const float* only_ptr(const float* p) { return p; }
+
+template <int S, int SKIP, int SL, bool CARRY, typename... BnSkip>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_DW_WGS_PER_CU, TTK_DW_WGS_PER_CU)))
 dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_prev,
                                                           const float* __restrict__ skip_prev, float* __restrict__ a_out,
                                                           const float* __restrict__ w, float* __restrict__ y,
                                                           float* __restrict__ part, const float* __restrict__ pivot, int B, int H, int W, int C,
-                                                          int Ho, int Wo, int R, int nbands, int nslabs, int NI_, int NCT_, int TW) {
+                                                          int Ho, int Wo, int R, int nbands, int nslabs, int NI_, int NCT_, int TW, BnSkip... bn_skip) {
+  static_assert(sizeof...(BnSkip) == (SKIP == kSkipRaw ? 1 : 0), "bn_skip: the raw residual form's one extra argument");
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [NI][stage_rows][tile width + 2][SL] + reduction scratch
   constexpr int kSlab = SL, kSlabQuads = SL / 4, kPixSlots = kBlock / kSlabQuads, kQs = ilog2(kSlabQuads), kPs = ilog2(SL);
   const int tid = threadIdx.x, q = tid & (kSlabQuads - 1), slot = tid >> kQs;
@@ -235,6 +245,8 @@ dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_pre
   SlabWeights wr;
   wr.load(w, c0);
   const BnApply4 bn = BnApply4::load(bn_prev, C, c0);
+  BnApply4 bns = bn;
+  if constexpr (SKIP == kSkipRaw) bns = BnApply4::load(only_ptr(bn_skip...), C, c0);
   const float4 pv = pivot ? ld4(pivot + c0) : f4(0.f);  // the partial sums are those of y - pivot (ttk.h)
   D4 s1{0.0, 0.0, 0.0, 0.0}, s2{0.0, 0.0, 0.0, 0.0};
   const int NI = CARRY ? 1 : NI_, NCT = CARRY ? 1 : NCT_;  // (carry mode: one image per tile, full-width bands - constants for the compiler)
@@ -293,7 +305,8 @@ dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_pre
     // kernel touches HBM).
     const int nstage = nimg * ((int)PI - ov * Wp) * kSlabQuads;
     const unsigned ovpix = (unsigned)(ov * Wp);
-    constexpr int kFwdU = SKIP ? kFwdUSkip : (S == 2 ? kFwdUPlain2 : (CARRY ? kFwdUPlain - 1 : kFwdUPlain));  // (carry mode holds five more float4 across the barrier)
+    // (carry mode holds five more float4 across the barrier; beside them and the second constant block of a raw residual operand, stride 1, three fit without scratch)
+    constexpr int kFwdU = SKIP ? (SKIP == kSkipRaw && S == 1 && CARRY ? kFwdUSkip - 1 : kFwdUSkip) : (S == 2 ? kFwdUPlain2 : (CARRY ? kFwdUPlain - 1 : kFwdUPlain));
     for (int e = tid; e < nstage; e += kFwdU * kBlock) {
       float4 yv[kFwdU], sk[SKIP ? kFwdU : 1];
       unsigned off[kFwdU];
@@ -319,7 +332,8 @@ dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_pre
         if (ee >= nstage) break;
         float4 a = f4(0.f);
         if (in[u]) {
-          if constexpr (SKIP) a = bn.act(yv[u], sk[u]);
+          if constexpr (SKIP == kSkipRaw) a = bn.act(yv[u], bns.act(sk[u]));
+          else if constexpr (SKIP == kSkipStored) a = bn.act(yv[u], sk[u]);
           else a = bn.act(yv[u]);
           if (S == 1 && a_out && rows[u]) st4(aotile + off[u], a);  // a materialised block input (residual, backward)
         }
@@ -365,7 +379,9 @@ dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_pre
 #ifndef TTK_DW_BWD_LEAN_PIX2
 #define TTK_DW_BWD_LEAN_PIX2 4  // stride 2 (6 measured slower: 276 vs 263 us on the 65 x 65 x 64 layer)
 #endif
-template <int S, int SL, bool LEAN, bool CARRY>
+// BnSkip (zero or one `const float*`, as in the forward kernel; non-LEAN, a_in null): skip_prev is the RAW convolution output behind the residual
+// operand and bn_skip its BatchNorm constant block.
+template <int S, int SL, bool LEAN, bool CARRY, typename... BnSkip>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_DW_WGS_PER_CU, TTK_DW_WGS_PER_CU)))  // <= 168 VGPRs: 3 workgroups per CU, as the LDS tile allows
 dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
                                                           const float* __restrict__ bn_dw, const float* __restrict__ w,
@@ -374,7 +390,9 @@ dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
                                                           const float* __restrict__ skip_prev, const float* __restrict__ a_in,
                                                           float* __restrict__ g_prev, float* __restrict__ part,
                                                           float* __restrict__ dwgrad, float* __restrict__ dw_partial, int B, int H, int W, int C, int Ho, int Wo,
-                                                          int R, int nbands, int nslabs, int stage_floats, int NI_, int NCT_, int TW, int ring) {
+                                                          int R, int nbands, int nslabs, int stage_floats, int NI_, int NCT_, int TW, int ring, BnSkip... bn_skip) {
+  constexpr bool RAWSKIP = sizeof...(BnSkip) == 1;
+  static_assert(sizeof...(BnSkip) <= 1 && !(RAWSKIP && LEAN), "bn_skip: the raw residual form's one extra argument");
   extern __shared__ __attribute__((aligned(16))) float lds[];  // dy[NI][stage_rows][Wo+2][SL] + reduction scratch
   const int NI = CARRY ? 1 : NI_, NCT = CARRY ? 1 : NCT_;  // (carry mode: one image per tile, full-width bands)
   constexpr int kSlab = SL, kSlabQuads = SL / 4, kPixSlots = kBlock / kSlabQuads, kQs = ilog2(kSlabQuads), kPs = ilog2(SL);
@@ -391,6 +409,8 @@ dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
   static_assert(SL == kCB, "a slab is one channel block of the activation layout");
   constexpr int cshift = 5;  // pixels of a channel block are 32 elements apart (ttk_common.h act_off)
   const BnApply4 bnp = BnApply4::load(bn_prev, C, c0);
+  BnApply4 bns = bnp;
+  if constexpr (RAWSKIP) bns = BnApply4::load(only_ptr(bn_skip...), C, c0);
   const BnGrad4 bg = BnGrad4::load(bn_dw, C, c0);
   D4 s1{0.0, 0.0, 0.0, 0.0}, s2{0.0, 0.0, 0.0, 0.0};
   float gmx = 0.f;  // max |g_prev|: the magnitude bound the previous block's fp16-split GEMMs scale by (ttk.h, TTK_AUX_GMAX)
@@ -439,7 +459,9 @@ dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
     // iteration (2 kBwdU loads in flight)
     const unsigned ovpix = (unsigned)(ov * Wp);
     const int nstage = nimg * ((int)PI - (int)ovpix) * kSlabQuads;
-    constexpr int kBwdU = TTK_DW_BWD_U;  // staged elements per thread and iteration: 2 * kBwdU loads in flight
+    // staged elements per thread and iteration: 2 * kBwdU loads in flight (raw residual operand, stride 1, no ring: two - with its second constant
+    // block four spilled 24 bytes and three 8; no layer of the default network runs that instantiation)
+    constexpr int kBwdU = (RAWSKIP && S == 1 && !CARRY) ? TTK_DW_BWD_U - 2 : TTK_DW_BWD_U;
     for (int e = tid; e < nstage; e += kBwdU * kBlock) {
       float4 gv[kBwdU], yv[kBwdU];
       bool in[kBwdU];
@@ -512,7 +534,8 @@ dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
         const float* dyimg = lds + (__umul24(imgs[j], PI) << kPs);
         const float4 yp = yps[j], raw = raws[j], sg = sgs[j];
         float4 a;
-        if (!LEAN && a_in) a = raw;
+        if constexpr (RAWSKIP) a = bnp.act(yp, bns.act(raw));
+        else if (!LEAN && a_in) a = raw;
         else a = (!LEAN && skip_prev) ? bnp.act(yp, raw) : bnp.act(yp);
         float4 G = f4(0.f);
 #pragma unroll
@@ -596,60 +619,101 @@ int ttk_partial_rows_dwconv(int B, int H, int W, int C, int stride, int backward
   return dw_tiling(B, H, W, C, stride, backward != 0).rows;
 }
 
-int ttk_dwconv3x3_fwd(const float* yprev, const float* bn_prev, const float* skip_prev, float* a_out, const float* w, float* y,
-                      float* part, const float* pivot, int B, int H, int W, int C, int stride, int act_bf16, ttk_stream_t stream) {
-  TTK_REQUIRE(yprev && bn_prev && w && y, "dwconv3x3_fwd: null pointer");
-  TTK_REQUIRE(dw_shape_ok2(B, H, W, C, stride), "dwconv3x3_fwd: unsupported shape B=%d H=%d W=%d C=%d stride=%d (C: power of two in 32..1024, W <= 256)", B, H, W, C, stride);
-  TTK_REQUIRE(!(a_out && stride != 1), "dwconv3x3_fwd: a_out requires stride 1");
-  TTK_REQUIRE_FP32_STORAGE(act_bf16, "dwconv3x3_fwd");
+// ttk_dwconv3x3_fwd and ttk_dwconv3x3_fwd_rawskip (raw = the residual operand is a raw convolution output + skip_bn)
+static int dw_fwd_launch(const char* name, bool raw, const float* yprev, const float* bn_prev, const float* skip_prev, const float* skip_bn, float* a_out,
+                         const float* w, float* y, float* part, const float* pivot, int B, int H, int W, int C, int stride, int act_bf16, ttk_stream_t stream) {
+  TTK_REQUIRE(yprev && bn_prev && w && y && (!raw || (skip_prev && skip_bn)), "%s: null pointer", name);
+  TTK_REQUIRE(dw_shape_ok2(B, H, W, C, stride), "%s: unsupported shape B=%d H=%d W=%d C=%d stride=%d (C: power of two in 32..1024, W <= 256)", name, B, H, W, C, stride);
+  TTK_REQUIRE(!(a_out && stride != 1), "%s: a_out requires stride 1", name);
+  TTK_REQUIRE((act_bf16 & 3) == 0, "%s: bf16 activation storage under the fp32 kernels was retired (round 6): use the bf16-compute path (ttk_bc_*)", name);
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const DwTiling t = dw_tiling(B, H, W, C, stride, false);
-  TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "dwconv3x3_fwd: too many tiles for 32-bit indexing");
+  TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "%s: too many tiles for 32-bit indexing", name);
   const size_t stage = (size_t)t.NI * t.stage_rows * ((t.NCT > 1 ? t.TW : W) + 2) * t.SL;
   const size_t sm = (stage + 16 * t.SL) * sizeof(float);  // + [4][2][SL] doubles of reduction scratch
-  // the specialisation <stride 1 | 2, residual input, slab = kCB, carry mode>
+  // the specialisation <stride 1 | 2, residual input (none | stored | raw), slab = kCB, carry mode>
   with_flag(stride == 2, [&](auto s2) {
-    with_flag(skip_prev != nullptr, [&](auto skip) {
-      with_flag(t.carry != 0, [&](auto carry) {
-        hipLaunchKernelGGL((dw_fwd_tiled_k<decltype(s2)::value ? 2 : 1, decltype(skip)::value, kCB, decltype(carry)::value>), dim3(t.grid), dim3(kBlock), sm,
-                           (hipStream_t)stream, yprev, bn_prev, skip_prev, a_out, w, y, part, pivot, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, t.NI,
-                           t.NCT, t.TW);
-      });
+    with_flag(t.carry != 0, [&](auto carry) {
+      constexpr int S = decltype(s2)::value ? 2 : 1;
+      constexpr bool CARRY = decltype(carry)::value;
+      if (raw) {
+        hipLaunchKernelGGL((dw_fwd_tiled_k<S, kSkipRaw, kCB, CARRY, const float*>), dim3(t.grid), dim3(kBlock), sm, (hipStream_t)stream, yprev, bn_prev, skip_prev,
+                           a_out, w, y, part, pivot, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, t.NI, t.NCT, t.TW, skip_bn);
+      } else {
+        with_flag(skip_prev != nullptr, [&](auto skip) {
+          hipLaunchKernelGGL((dw_fwd_tiled_k<S, decltype(skip)::value ? kSkipStored : kSkipNone, kCB, CARRY>), dim3(t.grid), dim3(kBlock), sm, (hipStream_t)stream, yprev, bn_prev, skip_prev,
+                             a_out, w, y, part, pivot, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, t.NI, t.NCT, t.TW);
+        });
+      }
     });
   });
-  TTK_LAUNCH_CHECK("dwconv3x3_fwd");
+  TTK_LAUNCH_CHECK(name);
+}
+
+int ttk_dwconv3x3_fwd(const float* yprev, const float* bn_prev, const float* skip_prev, float* a_out, const float* w, float* y,
+                      float* part, const float* pivot, int B, int H, int W, int C, int stride, int act_bf16, ttk_stream_t stream) {
+  return dw_fwd_launch("dwconv3x3_fwd", false, yprev, bn_prev, skip_prev, nullptr, a_out, w, y, part, pivot, B, H, W, C, stride, act_bf16, stream);
+}
+
+int ttk_dwconv3x3_fwd_rawskip(const float* yprev, const float* bn_prev, const float* skip_raw, const float* skip_bn, float* a_out, const float* w, float* y,
+                              float* part, const float* pivot, int B, int H, int W, int C, int stride, ttk_stream_t stream) {
+  return dw_fwd_launch("dwconv3x3_fwd_rawskip", true, yprev, bn_prev, skip_raw, skip_bn, a_out, w, y, part, pivot, B, H, W, C, stride, 0, stream);
+}
+
+// ttk_dwconv3x3_bwd_data and ttk_dwconv3x3_bwd_data_rawskip (raw = skip_prev is a raw convolution output + skip_bn; no a_in)
+static int dw_bwd_launch(const char* name, bool raw, const float* g_dw, const float* y_dw, const float* bn_dw, const float* w, const float* skip_grad,
+                         const float* yprev, float* bn_prev, const float* skip_prev, const float* skip_bn, const float* a_in, float* g_prev, float* part, float* dw,
+                         int dw_accumulate, float* dw_partial, int B, int H, int W, int C, int stride, int act_bf16, ttk_stream_t stream) {
+  TTK_REQUIRE(g_dw && y_dw && bn_dw && w && yprev && bn_prev && g_prev && (!raw || (skip_prev && skip_bn)), "%s: null pointer", name);
+  TTK_REQUIRE(dw_shape_ok2(B, H, W, C, stride), "%s: unsupported shape", name);
+  TTK_REQUIRE(!(skip_grad && stride != 1), "%s: residual gradient requires stride 1", name);
+  TTK_REQUIRE((act_bf16 & 3) == 0, "%s: bf16 activation storage under the fp32 kernels was retired (round 6): use the bf16-compute path (ttk_bc_*)", name);
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  const DwTiling t = dw_tiling(B, H, W, C, stride, true);
+  TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "%s: too many tiles for 32-bit indexing", name);
+  const size_t stage = (size_t)t.NI * t.stage_rows * ((t.NCT > 1 ? t.TW : Wo) + 2) * t.SL;
+  const size_t sm = (stage + 4 * 9 * t.SL + 9 * t.SL) * sizeof(float);  // stage + reduction scratch + filter taps
+  hipStream_t st = (hipStream_t)stream;
+  if (!dw) dw_partial = nullptr;
+  TTK_REQUIRE(dw_accumulate != 2 || dw_partial, "%s: dw_accumulate = 2 (rows folded by the caller) needs dw and dw_partial", name);
+  if (dw && !dw_accumulate && !dw_partial) hipLaunchKernelGGL(zero_fill_k, dim3((9 * C + 255) / 256), dim3(256), 0, st, dw, (int64_t)9 * C);
+  // the specialisation <stride 1 | 2, slab = kCB, no residual operands, carry mode> (raw residual operand: never lean, one more argument)
+  with_flag(stride == 2, [&](auto s2) {
+    with_flag(t.carry != 0, [&](auto carry) {
+      constexpr int S = decltype(s2)::value ? 2 : 1;
+      constexpr bool CARRY = decltype(carry)::value;
+      if (raw) {
+        hipLaunchKernelGGL((dw_bwd_tiled_k<S, kCB, false, CARRY, const float*>), dim3(t.grid), dim3(kBlock), sm, st, g_dw, y_dw, bn_dw, w, skip_grad, yprev, bn_prev,
+                           skip_prev, a_in, g_prev, part, dw, dw_partial, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, (int)stage, t.NI, t.NCT, t.TW, t.stage_rows,
+                           skip_bn);
+      } else {
+        with_flag(!a_in && !skip_prev && !skip_grad, [&](auto lean) {
+          hipLaunchKernelGGL((dw_bwd_tiled_k<S, kCB, decltype(lean)::value, CARRY>), dim3(t.grid), dim3(kBlock), sm, st, g_dw, y_dw, bn_dw, w, skip_grad, yprev,
+                             bn_prev, skip_prev, a_in, g_prev, part, dw, dw_partial, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, (int)stage, t.NI, t.NCT, t.TW,
+                             t.stage_rows);
+        });
+      }
+    });
+  });
+  // dw_accumulate == 2: the rows stay unfolded - the caller folds them beside the BatchNorm-backward finalisation (ttk_bc_bn_bwd_finalize_fold)
+  if (dw_partial && dw_accumulate != 2) launch_fold_partials(dw_partial, t.rows, (int64_t)9 * C, dw, dw_accumulate, st);
+  TTK_LAUNCH_CHECK(name);
 }
 
 int ttk_dwconv3x3_bwd_data(const float* g_dw, const float* y_dw, const float* bn_dw, const float* w, const float* skip_grad,
                            const float* yprev, float* bn_prev, const float* skip_prev, const float* a_in, float* g_prev,
                            float* part, float* dw, int dw_accumulate, float* dw_partial, int B, int H, int W, int C, int stride,
                            int act_bf16, ttk_stream_t stream) {
-  TTK_REQUIRE(g_dw && y_dw && bn_dw && w && yprev && bn_prev && g_prev, "dwconv3x3_bwd_data: null pointer");
-  TTK_REQUIRE(dw_shape_ok2(B, H, W, C, stride), "dwconv3x3_bwd_data: unsupported shape");
-  TTK_REQUIRE(!(skip_grad && stride != 1), "dwconv3x3_bwd_data: residual gradient requires stride 1");
-  TTK_REQUIRE_FP32_STORAGE(act_bf16, "dwconv3x3_bwd_data");
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const DwTiling t = dw_tiling(B, H, W, C, stride, true);
-  TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "dwconv3x3_bwd_data: too many tiles for 32-bit indexing");
-  const size_t stage = (size_t)t.NI * t.stage_rows * ((t.NCT > 1 ? t.TW : Wo) + 2) * t.SL;
-  const size_t sm = (stage + 4 * 9 * t.SL + 9 * t.SL) * sizeof(float);  // stage + reduction scratch + filter taps
-  hipStream_t st = (hipStream_t)stream;
-  if (!dw) dw_partial = nullptr;
-  TTK_REQUIRE(dw_accumulate != 2 || dw_partial, "dwconv3x3_bwd_data: dw_accumulate = 2 (rows folded by the caller) needs dw and dw_partial");
-  if (dw && !dw_accumulate && !dw_partial) hipLaunchKernelGGL(zero_fill_k, dim3((9 * C + 255) / 256), dim3(256), 0, st, dw, (int64_t)9 * C);
-  // the specialisation <stride 1 | 2, slab = kCB, no residual operands, carry mode>
-  with_flag(stride == 2, [&](auto s2) {
-    with_flag(!a_in && !skip_prev && !skip_grad, [&](auto lean) {
-      with_flag(t.carry != 0, [&](auto carry) {
-        hipLaunchKernelGGL((dw_bwd_tiled_k<decltype(s2)::value ? 2 : 1, kCB, decltype(lean)::value, decltype(carry)::value>), dim3(t.grid), dim3(kBlock), sm, st,
-                           g_dw, y_dw, bn_dw, w, skip_grad, yprev, bn_prev, skip_prev, a_in, g_prev, part, dw, dw_partial, B, H, W, C, Ho, Wo, t.R,
-                           t.nbands, t.nslabs, (int)stage, t.NI, t.NCT, t.TW, t.stage_rows);
-      });
-    });
-  });
-  // dw_accumulate == 2: the rows stay unfolded - the caller folds them beside the BatchNorm-backward finalisation (ttk_bc_bn_bwd_finalize_fold)
-  if (dw_partial && dw_accumulate != 2) launch_fold_partials(dw_partial, t.rows, (int64_t)9 * C, dw, dw_accumulate, st);
-  TTK_LAUNCH_CHECK("dwconv3x3_bwd_data");
+  return dw_bwd_launch("dwconv3x3_bwd_data", false, g_dw, y_dw, bn_dw, w, skip_grad, yprev, bn_prev, skip_prev, nullptr, a_in, g_prev, part, dw, dw_accumulate,
+                       dw_partial, B, H, W, C, stride, act_bf16, stream);
+}
+
+int ttk_dwconv3x3_bwd_data_rawskip(const float* g_dw, const float* y_dw, const float* bn_dw, const float* w, const float* skip_grad,
+                                   const float* yprev, float* bn_prev, const float* skip_raw, const float* skip_bn, float* g_prev,
+                                   float* part, float* dw, int dw_accumulate, float* dw_partial, int B, int H, int W, int C, int stride,
+                                   ttk_stream_t stream) {
+  return dw_bwd_launch("dwconv3x3_bwd_data_rawskip", true, g_dw, y_dw, bn_dw, w, skip_grad, yprev, bn_prev, skip_raw, skip_bn, nullptr, g_prev, part, dw,
+                       dw_accumulate, dw_partial, B, H, W, C, stride, 0, stream);
 }
 
 }  // extern "C"

@@ -14,10 +14,17 @@ __device__ __forceinline__ size_t pool_off(int layout, int64_t m, int c, int64_t
   return act_off(m, c, M);
 }
 
+// BnSkip (both kernels): zero or one `const float* bn_skip`.  With it, `skip` is the RAW convolution output behind the residual operand and
+// bn_skip its BatchNorm constant block - the operand relu(bn_skip(skip)) is formed on load (csrc/dwconv_tiled.hip, kSkipRaw: the last block
+// heads a residual chain and its input is not stored).
+__device__ __forceinline__ const float* only_ptr(const float* p) { return p; }
+
 // thread = (sample, channel quad)
+template <typename... BnSkip>
 __global__ void __launch_bounds__(kBlock) avgpool_fwd_k(const float* __restrict__ y, const float* __restrict__ bnp,
                                                          const float* __restrict__ skip,
-                                                         float* __restrict__ feat, int B, int HW, int C, int rows_layout) {
+                                                         float* __restrict__ feat, int B, int HW, int C, int rows_layout, BnSkip... bn_skip) {
+  constexpr bool RAW = sizeof...(BnSkip) == 1;
   const int quads = C >> 2;
   const int64_t items = (int64_t)B * quads;
   const float inv = 1.0f / (float)HW;
@@ -25,24 +32,31 @@ __global__ void __launch_bounds__(kBlock) avgpool_fwd_k(const float* __restrict_
     const int c4 = (int)(idx % quads);
     const int n = (int)(idx / quads);
     const BnApply4 bn = BnApply4::load(bnp, C, 4 * c4);
+    BnApply4 bs = bn;
+    if constexpr (RAW) bs = BnApply4::load(only_ptr(bn_skip...), C, 4 * c4);
     float4 s = f4(0.f);
     for (int p = 0; p < HW; ++p) {
       const int64_t m = (int64_t)n * HW + p;
       const size_t off = pool_off(rows_layout, m, 4 * c4, (int64_t)B * HW, C);
-      s = add4(s, skip ? bn.act(ld4(y + off), ld4(skip + off)) : bn.act(ld4(y + off)));
+      if constexpr (RAW) s = add4(s, bn.act(ld4(y + off), bs.act(ld4(skip + off))));
+      else s = add4(s, skip ? bn.act(ld4(y + off), ld4(skip + off)) : bn.act(ld4(y + off)));
     }
     st4(feat + (size_t)n * C + 4 * c4, make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv));
   }
 }
 
 // thread = (sample, pixel, channel quad)
+template <typename... BnSkip>
 __global__ void __launch_bounds__(kBlock) avgpool_bwd_k(const float* __restrict__ gfeat, const float* __restrict__ y,
                                                          float* __restrict__ bnp, const float* __restrict__ skip, float* __restrict__ g,
-                                                         float* __restrict__ part, int B, int HW, int C, int qshift, int rows_layout) {
+                                                         float* __restrict__ part, int B, int HW, int C, int qshift, int rows_layout, BnSkip... bn_skip) {
+  constexpr bool RAW = sizeof...(BnSkip) == 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int quads = C >> 2;
   const int c4 = threadIdx.x & (quads - 1);
   const BnApply4 bn = BnApply4::load(bnp, C, 4 * c4);
+  BnApply4 bs = bn;
+  if constexpr (RAW) bs = BnApply4::load(only_ptr(bn_skip...), C, 4 * c4);
   const float inv = 1.0f / (float)HW;
   const int64_t items = ((int64_t)B * HW) << qshift;
   float4 s1 = f4(0.f), s2 = f4(0.f);
@@ -51,7 +65,9 @@ __global__ void __launch_bounds__(kBlock) avgpool_bwd_k(const float* __restrict_
     const int n = (int)((unsigned)(idx >> qshift) / (unsigned)HW);  // 32-bit division (the host checks that B * HW fits)
     const size_t off = pool_off(rows_layout, idx >> qshift, 4 * c4, (int64_t)B * HW, C);
     const float4 yv = ld4(y + off);
-    const float4 a = skip ? bn.act(yv, ld4(skip + off)) : bn.act(yv);
+    float4 a;
+    if constexpr (RAW) a = bn.act(yv, bs.act(ld4(skip + off)));
+    else a = skip ? bn.act(yv, ld4(skip + off)) : bn.act(yv);
     float4 gv = ld4(gfeat + (size_t)n * C + 4 * c4);
     gv = mask4(make_float4(gv.x * inv, gv.y * inv, gv.z * inv, gv.w * inv), a);
     st4(g + off, gv);
@@ -83,28 +99,60 @@ static int log2i_(int v) {
 
 extern "C" {
 
+// ttk_avgpool_fwd and ttk_avgpool_fwd_rawskip (skip_bn != NULL: `skip` is a raw convolution output)
+static int avgpool_fwd_launch(const char* name, const float* y, const float* bn, const float* skip, const float* skip_bn, float* feat, int B, int HW, int C,
+                              int act_bf16, ttk_stream_t stream) {
+  TTK_REQUIRE(y && bn && feat, "%s: null pointer", name);
+  TTK_REQUIRE(B > 0 && HW > 0 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0, "%s: unsupported shape B=%d HW=%d C=%d", name, B, HW, C);
+  TTK_REQUIRE((act_bf16 & 3) == 0, "%s: bf16 activation storage under the fp32 kernels was retired (round 6): use the bf16-compute path (ttk_bc_*)", name);
+  const int64_t items = (int64_t)B * (C / 4);
+  if (skip_bn)
+    hipLaunchKernelGGL((avgpool_fwd_k<const float*>), dim3(elementwise_grid(items)), dim3(kBlock), 0, (hipStream_t)stream, y, bn, skip, feat, B, HW, C,
+                       pool_layout(act_bf16), skip_bn);
+  else
+    hipLaunchKernelGGL((avgpool_fwd_k<>), dim3(elementwise_grid(items)), dim3(kBlock), 0, (hipStream_t)stream, y, bn, skip, feat, B, HW, C,
+                       pool_layout(act_bf16));
+  TTK_LAUNCH_CHECK(name);
+}
+
 int ttk_avgpool_fwd(const float* y, const float* bn, const float* skip, float* feat, int B, int HW,
                     int C, int act_bf16, ttk_stream_t stream) {
-  TTK_REQUIRE(y && bn && feat, "avgpool_fwd: null pointer");
-  TTK_REQUIRE(B > 0 && HW > 0 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0, "avgpool_fwd: unsupported shape B=%d HW=%d C=%d", B, HW, C);
-  TTK_REQUIRE_FP32_STORAGE(act_bf16, "avgpool_fwd");
-  const int64_t items = (int64_t)B * (C / 4);
-  hipLaunchKernelGGL(avgpool_fwd_k, dim3(elementwise_grid(items)), dim3(kBlock), 0, (hipStream_t)stream, y, bn, skip, feat, B, HW, C,
-                     pool_layout(act_bf16));
-  TTK_LAUNCH_CHECK("avgpool_fwd");
+  return avgpool_fwd_launch("avgpool_fwd", y, bn, skip, nullptr, feat, B, HW, C, act_bf16, stream);
+}
+
+int ttk_avgpool_fwd_rawskip(const float* y, const float* bn, const float* skip_raw, const float* skip_bn, float* feat, int B, int HW,
+                            int C, ttk_stream_t stream) {
+  TTK_REQUIRE(skip_raw && skip_bn, "avgpool_fwd_rawskip: null pointer");
+  return avgpool_fwd_launch("avgpool_fwd_rawskip", y, bn, skip_raw, skip_bn, feat, B, HW, C, 0, stream);
+}
+
+// ttk_avgpool_bwd and ttk_avgpool_bwd_rawskip (skip_bn != NULL: `skip` is a raw convolution output)
+static int avgpool_bwd_launch(const char* name, const float* gfeat, const float* y, float* bn, const float* skip, const float* skip_bn, float* g, float* part,
+                              int B, int HW, int C, int act_bf16, ttk_stream_t stream) {
+  TTK_REQUIRE(gfeat && y && bn && g, "%s: null pointer", name);
+  TTK_REQUIRE(B > 0 && HW > 0 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0, "%s: unsupported shape", name);
+  TTK_REQUIRE((int64_t)B * HW < (int64_t)1 << 31, "%s: too many pixels for 32-bit indexing", name);
+  TTK_REQUIRE((act_bf16 & 3) == 0, "%s: bf16 activation storage under the fp32 kernels was retired (round 6): use the bf16-compute path (ttk_bc_*)", name);
+  const int qs = log2i_(C / 4);
+  const int64_t items = ((int64_t)B * HW) << qs;
+  if (skip_bn)
+    hipLaunchKernelGGL((avgpool_bwd_k<const float*>), dim3(elementwise_grid(items)), dim3(kBlock), 2 * (size_t)C * sizeof(float), (hipStream_t)stream, gfeat, y,
+                       bn, skip, g, part, B, HW, C, qs, pool_layout(act_bf16), skip_bn);
+  else
+    hipLaunchKernelGGL((avgpool_bwd_k<>), dim3(elementwise_grid(items)), dim3(kBlock), 2 * (size_t)C * sizeof(float), (hipStream_t)stream, gfeat, y, bn,
+                       skip, g, part, B, HW, C, qs, pool_layout(act_bf16));
+  TTK_LAUNCH_CHECK(name);
 }
 
 int ttk_avgpool_bwd(const float* gfeat, const float* y, float* bn, const float* skip, float* g,
                     float* part, int B, int HW, int C, int act_bf16, ttk_stream_t stream) {
-  TTK_REQUIRE(gfeat && y && bn && g, "avgpool_bwd: null pointer");
-  TTK_REQUIRE(B > 0 && HW > 0 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0, "avgpool_bwd: unsupported shape");
-  TTK_REQUIRE((int64_t)B * HW < (int64_t)1 << 31, "avgpool_bwd: too many pixels for 32-bit indexing");
-  TTK_REQUIRE_FP32_STORAGE(act_bf16, "avgpool_bwd");
-  const int qs = log2i_(C / 4);
-  const int64_t items = ((int64_t)B * HW) << qs;
-  hipLaunchKernelGGL(avgpool_bwd_k, dim3(elementwise_grid(items)), dim3(kBlock), 2 * (size_t)C * sizeof(float), (hipStream_t)stream, gfeat, y, bn,
-                     skip, g, part, B, HW, C, qs, pool_layout(act_bf16));
-  TTK_LAUNCH_CHECK("avgpool_bwd");
+  return avgpool_bwd_launch("avgpool_bwd", gfeat, y, bn, skip, nullptr, g, part, B, HW, C, act_bf16, stream);
+}
+
+int ttk_avgpool_bwd_rawskip(const float* gfeat, const float* y, float* bn, const float* skip_raw, const float* skip_bn, float* g,
+                            float* part, int B, int HW, int C, ttk_stream_t stream) {
+  TTK_REQUIRE(skip_raw && skip_bn, "avgpool_bwd_rawskip: null pointer");
+  return avgpool_bwd_launch("avgpool_bwd_rawskip", gfeat, y, bn, skip_raw, skip_bn, g, part, B, HW, C, 0, stream);
 }
 
 }  // extern "C"

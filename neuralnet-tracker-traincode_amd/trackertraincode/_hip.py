@@ -29,6 +29,8 @@ _SIGNATURES = {
     "ttk_stem_bwd_weight": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I],
     "ttk_dwconv3x3_fwd": [_P] * 8 + [_I] * 6,
     "ttk_dwconv3x3_bwd_data": [_P] * 12 + [_I, _P] + [_I] * 6,
+    "ttk_dwconv3x3_fwd_rawskip": [_P] * 9 + [_I] * 5,
+    "ttk_dwconv3x3_bwd_data_rawskip": [_P] * 12 + [_I, _P] + [_I] * 5,
     "ttk_pwconv1x1_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _I],
     "ttk_pwconv1x1_bwd_data": [_P] * 8 + [_L, _I, _I, _P, _I],
     "ttk_pwconv1x1_bwd_weight": [_P] * 7 + [_L, _I, _I, _I],
@@ -37,6 +39,8 @@ _SIGNATURES = {
     "ttk_transpose": [_P, _P, _I, _I],
     "ttk_avgpool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I],
     "ttk_avgpool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
+    "ttk_avgpool_fwd_rawskip": [_P, _P, _P, _P, _P, _I, _I, _I],
+    "ttk_avgpool_bwd_rawskip": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I],
     "ttk_bn_act": [_P, _P, _P, _P, _L, _I],
     "ttk_stem7_fwd": [_P, _P, _P, _P, _P, _I, _I, _I],
     "ttk_stem7_bwd_weight": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
@@ -124,7 +128,7 @@ _SIGNATURES = {
     "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 # Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the

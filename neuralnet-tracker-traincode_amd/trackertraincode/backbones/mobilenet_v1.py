@@ -169,6 +169,7 @@ class _Stage(NamedTuple):
     y: torch.Tensor            # raw conv output [B,H,W,C]
     bn: torch.Tensor           # BatchNorm constant block [8, C]
     skip: torch.Tensor | None  # residual input added before the ReLU of this stage's output
+    skip_bn: torch.Tensor | None = None  # None: `skip` is a stored activation; else `skip` is a RAW conv output and this its constant block (ttk_*_rawskip)
 
 
 def _part_buffer(B, H, W, device, blur=False, blocks=_BLOCKS, c0=_STEM_CHANNELS):
@@ -288,10 +289,14 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
     ctx.stages.append(prev)
     h, w_ = Ho, Wo
     pi, bi = 3, 1
-    def dw_fwd(yprev, bn_prev, skip_prev, a_out, w, y, pv, hh, ww, C, stride):
-        """One depthwise launch -> the rows of partial sums it wrote."""
+    def dw_fwd(st, a_out, w, y, pv, hh, ww, C, stride):
+        """One depthwise launch on the output of stage `st` -> the rows of partial sums it wrote."""
+        yprev, bn_prev, skip_prev = st.y, st.bn, st.skip
         if _tuned_c(C):
-            L.call("ttk_dwconv3x3_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride, bf)
+            if st.skip_bn is not None:
+                L.call("ttk_dwconv3x3_fwd_rawskip", p(yprev), p(bn_prev), p(skip_prev), p(st.skip_bn), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride)
+            else:
+                L.call("ttk_dwconv3x3_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride, bf)
             return L.partial_rows_dwconv(B, hh, ww, C, stride, False)
         L.call("ttk_anyc_dw_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride)
         return L.anyc_partial_rows(B * ((hh - 1) // stride + 1) * ((ww - 1) // stride + 1))
@@ -301,7 +306,12 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
         pi += 6
         has_skip = stride == 1 and cin == cout
         ho, wo = (h - 1) // stride + 1, (w_ - 1) // stride + 1
-        a_in = torch.empty_like(prev.y) if has_skip else None
+        # The input of a residual block is stored (a_in: written by its depthwise forward, read back by its depthwise backward) - except for the
+        # FIRST block of a chain where _ELIDE_HEAD_INPUT says so: its input relu(bn(y_prev)) has no residual of its own, every consumer either
+        # loads y_prev already or loads it in place of the stored tensor (the raw residual operand, include/ttk.h).  (The any-channel-count
+        # family keeps storing.)
+        head = has_skip and prev.skip is None and _tuned_c(cin) and (_ELIDE_HEAD_INPUT is True or (bool(_ELIDE_HEAD_INPUT) and name in _ELIDE_HEAD_INPUT))
+        a_in = torch.empty_like(prev.y) if (has_skip and not head) else None
         ydw = torch.empty((B, ho, wo, cin), dtype=act_dtype, device=dev)
         k = len(ctx.dims)
         if blur[k] is not None:
@@ -309,12 +319,12 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
             # same depthwise kernel; the blurred tensor crosses HBM once with the identity constant block (its partial sums
             # are written to the scratch rows and overwritten by the next launch)
             t = torch.empty((B, ho, wo, cin), dtype=act_dtype, device=dev)
-            dw_fwd(prev.y, prev.bn, prev.skip, None, blur[k], t, None, h, w_, cin, stride)
+            dw_fwd(prev, None, blur[k], t, None, h, w_, cin, stride)
             st_t = _Stage(t, _identity_bn(cin, dev), None)
-            dw_rows = dw_fwd(t, st_t.bn, None, None, w_dw, ydw, pivot(bi), ho, wo, cin, 1)
+            dw_rows = dw_fwd(st_t, None, w_dw, ydw, pivot(bi), ho, wo, cin, 1)
             ctx.blur.append((st_t, blur[k]))
         else:
-            dw_rows = dw_fwd(prev.y, prev.bn, prev.skip, a_in, w_dw, ydw, pivot(bi), h, w_, cin, stride)
+            dw_rows = dw_fwd(prev, a_in, w_dw, ydw, pivot(bi), h, w_, cin, stride)
             ctx.blur.append(None)
         if _EXP_TENSOR_HOOK is not None:
             _EXP_TENSOR_HOOK("y", k, ydw)
@@ -334,14 +344,16 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
         finalize(bn_pw, pw_rows, cout, M, g_pw, b_pw, bi + 1)
         bi += 2
         ctx.stages.append(_Stage(ydw, bn_dw, None))
-        prev = _Stage(ypw, bn_pw, a_in)
+        prev = _Stage(ypw, bn_pw, skip=prev.y, skip_bn=prev.bn) if head else _Stage(ypw, bn_pw, a_in)
         ctx.stages.append(prev)
         ctx.a_in.append(a_in)
         ctx.dims.append((h, w_, ho, wo, cin, cout, stride, has_skip))
         h, w_ = ho, wo
     C = prev.y.shape[-1]
     feat = torch.empty((B, C), dtype=torch.float32, device=dev)
-    if _tuned_c(C):
+    if _tuned_c(C) and prev.skip_bn is not None:
+        L.call("ttk_avgpool_fwd_rawskip", p(prev.y), p(prev.bn), p(prev.skip), p(prev.skip_bn), p(feat), B, h * w_, C)
+    elif _tuned_c(C):
         L.call("ttk_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C, bf)
     else:
         L.call("ttk_anyc_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C)
@@ -366,6 +378,12 @@ _USE_WGRAD_STREAM = False
 # by a second kernel instead of fp32 atomics): two runs of a step give bitwise equal gradients.
 _DETERMINISTIC = os.environ.get("TTK_DETERMINISTIC", "0") != "0"
 _FUSED_PW_BWD = True
+# The first block of a chain of residual blocks (dw3_1, dw4_1, dw5_1, dw6) need not store its input: it is relu(bn(y)) of the producer alone, and its
+# consumers can form it on load (the ttk_*_rawskip entry points).  True: none of the four stores it; False: all do (the stored form: the A/B run,
+# tests/test_rawskip_gpu.py); a tuple of block names: those blocks do not.  The product elides the two large ones.  Behind dw5_1 and dw6 the raw form's
+# consumer measured slower than the stored one (the 9 x 9 x 512 forward of dw5_2 54.1 -> 60.1 us, the pool forward 22.7 -> 23.3 us: the stored input was
+# still in the memory-side cache, the raw tensor three launches back is not), so these two keep storing - profiles/head_block_input.txt.
+_ELIDE_HEAD_INPUT = ("dw3_1", "dw4_1")
 # The fused depthwise weight gradient: 0 = float atomics (the product until round 5), 1 = workgroup rows + their own fold launch (slower: 67.3 k against
 # 68.4 k crops/s), 2 = rows folded inside the launch that finalises the producer's BatchNorm backward (ttk_bc_bn_bwd_finalize_fold: 68.9 k, same box,
 # tools/exp/ab_dw_rows_fp32.py) - the product.  Deterministic mode keeps its own scratch and fold order.
@@ -456,13 +474,26 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
 
     g = torch.empty(last.y.shape, dtype=ctx.gdt, device=last.y.device)
     if _tuned_c(C):
-        L.call("ttk_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C, bf)
+        if last.skip_bn is not None:
+            L.call("ttk_avgpool_bwd_rawskip", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(last.skip_bn), p(g), p(part), B, ctx.HW, C)
+        else:
+            L.call("ttk_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C, bf)
         bwd_finalize(last, L.partial_rows_elementwise(B * ctx.HW * (C // 4)), B * ctx.HW, len(params) - 2)
     else:
         L.call("ttk_anyc_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C)
         bwd_finalize(last, L.anyc_partial_rows(B * ctx.HW), B * ctx.HW, len(params) - 2)
     if _EXP_TENSOR_HOOK is not None:
         _EXP_TENSOR_HOOK("g", len(blocks), g)
+
+    def dw_bwd(g_dw, st_dw, w, skip_grad, st_prev, a_in, g_prev, dw, acc, rows, hh, ww, C, stride):
+        """One tuned depthwise data-gradient launch into the output of stage `st_prev` (its residual operand stored or raw)."""
+        if st_prev.skip_bn is not None and a_in is None:
+            L.call("ttk_dwconv3x3_bwd_data_rawskip", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w), p(skip_grad), p(st_prev.y), p(st_prev.bn), p(st_prev.skip),
+                   p(st_prev.skip_bn), p(g_prev), p(part), p(dw), acc, p(rows), B, hh, ww, C, stride)
+        else:
+            # (a stored a_in stands for the whole block input: the residual operand, stored or raw, is not read)
+            L.call("ttk_dwconv3x3_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w), p(skip_grad), p(st_prev.y), p(st_prev.bn),
+                   p(st_prev.skip if st_prev.skip_bn is None else None), p(a_in), p(g_prev), p(part), p(dw), acc, p(rows), B, hh, ww, C, stride, bf)
 
     for k in range(len(blocks) - 1, -1, -1):
         h, w_, ho, wo, cin, cout, stride, has_skip = ctx.dims[k]
@@ -537,23 +568,19 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
             # through the fixed blur kernel (no weight gradient) to the block input
             st_t, w_blur = ctx.blur[k]
             g_t = torch.empty(st_t.y.shape, dtype=ctx.gdt, device=st_t.y.device)
-            L.call("ttk_dwconv3x3_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), None, p(st_t.y), p(st_t.bn), None, None, p(g_t),
-                   p(part), p(dWd), 1, p(wg_scratch), B, ho, wo, cin, 1, bf)  # (float atomics unless deterministic: rows + an own fold launch measured slower)
+            dw_bwd(g_dw, st_dw, w_dw, None, st_t, None, g_t, dWd, 1, wg_scratch, ho, wo, cin, 1)  # (float atomics unless deterministic: rows + an own fold launch measured slower)
             L.call("ttk_bn_bwd_frozen", p(st_t.bn), cin)
-            L.call("ttk_dwconv3x3_bwd_data", p(g_t), p(st_t.y), p(st_t.bn), p(w_blur), None, p(st_prev.y), p(st_prev.bn), p(st_prev.skip),
-                   None, p(g_prev), p(part), None, 0, None, B, h, w_, cin, stride, bf)
+            dw_bwd(g_t, st_t, w_blur, None, st_prev, None, g_prev, None, 0, None, h, w_, cin, stride)
             bwd_finalize(st_prev, L.partial_rows_dwconv(B, h, w_, cin, stride, True), B * h * w_, pi - 2 if k > 0 else 1)
         elif _DW_WGRAD_ROWS == 2 and not _DETERMINISTIC and not ctx.frozen:
             # workgroup rows, folded by the launch that finalises the producer's BatchNorm backward (one launch instead of atomics + nothing / rows + fold)
             rows, gi = L.partial_rows_dwconv(B, h, w_, cin, stride, True), (pi - 2 if k > 0 else 1)
-            L.call("ttk_dwconv3x3_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), p(g) if has_skip else None, p(st_prev.y),
-                   p(st_prev.bn), p(st_prev.skip), p(a_in), p(g_prev), p(part), p(dWd), 2, p(dw_rows), B, h, w_, cin, stride, bf)
+            dw_bwd(g_dw, st_dw, w_dw, g if has_skip else None, st_prev, a_in, g_prev, dWd, 2, dw_rows, h, w_, cin, stride)
             L.call("ttk_bc_bn_bwd_finalize_fold", p(part), rows, cin, B * h * w_, p(params[gi]), p(st_prev.bn), p(grads[gi]), p(grads[gi + 1]), 0,
                    p(dw_rows), rows, 9 * cin, p(dWd), 1)
         else:
-            L.call("ttk_dwconv3x3_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), p(g) if has_skip else None, p(st_prev.y),
-                   p(st_prev.bn), p(st_prev.skip), p(a_in), p(g_prev), p(part), p(dWd), 1,
-                   p(dw_rows if (_DW_WGRAD_ROWS == 1 and not ctx.frozen) else wg_scratch), B, h, w_, cin, stride, bf)  # (_DW_WGRAD_ROWS = 1: the A/B form, rows + own fold)
+            dw_bwd(g_dw, st_dw, w_dw, g if has_skip else None, st_prev, a_in, g_prev, dWd, 1,
+                   dw_rows if (_DW_WGRAD_ROWS == 1 and not ctx.frozen) else wg_scratch, h, w_, cin, stride)  # (_DW_WGRAD_ROWS = 1: the A/B form, rows + own fold)
             bwd_finalize(st_prev, L.partial_rows_dwconv(B, h, w_, cin, stride, True), B * h * w_, pi - 2 if k > 0 else 1)
         g = g_prev
         if _EXP_TENSOR_HOOK is not None:
@@ -748,8 +775,13 @@ class MobileNet(nn.Module):
         for k, (name, *_r) in enumerate(self._blocks):
             if name in _INTERMEDIATES:
                 st = c.stages[2 * k + 2]
+                skip = st.skip
+                if st.skip_bn is not None:  # a raw residual operand: materialise relu(bn(skip)) first (an inspection path)
+                    skip = torch.empty_like(st.skip)
+                    L.call("ttk_bn_act", p(st.skip), p(st.skip_bn), None, p(skip), skip.numel() // skip.shape[-1], skip.shape[-1])
+                    skip = _hip.to_blocks(skip)
                 a = torch.empty_like(st.y)
-                L.call("ttk_bn_act" if _tuned_c(a.shape[-1]) else "ttk_anyc_bn_act", p(st.y), p(st.bn), p(st.skip), p(a), a.numel() // a.shape[-1], a.shape[-1])
+                L.call("ttk_bn_act" if _tuned_c(a.shape[-1]) else "ttk_anyc_bn_act", p(st.y), p(st.bn), p(skip), p(a), a.numel() // a.shape[-1], a.shape[-1])
                 outs.append(a.permute(0, 3, 1, 2))  # NCHW view of the channels-last copy ttk_bn_act wrote
         return outs
 
