@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 32
+#define TTK_ABI_VERSION 33
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -689,7 +689,14 @@ int ttk_clip_adam(const int64_t* ptrs, const int32_t* numel, const int32_t* grou
  *                      that a degenerate tr terminates); no atomics, bitwise reproducible.
  *   ttk_affine_labels  in place: coord[B][3], pose[B][4] (ijkw), roi[B][4] (nullable each), pts_in ->
  *                      pts_out [B][68][3] (68-point flip map when det < 0); with N > 0 followed by the
- *                      pixel -> [-1,1] normalisation of normalize_batch (batch/normalization.py:20-56)
+ *                      pixel -> [-1,1] normalisation of normalize_batch (batch/normalization.py:20-56).
+ *                      pts_in and pts_out may be the same buffer only where no sample's tr has det < 0.
+ *   ttk_affine_labels2d (ABI 33) ttk_affine_labels plus a second, 2-D landmark field (the reference transforms every point
+ *                      field, 2-D ones included: tensors/affinetrafo.py:51-52, 70-71): pts2d_in -> pts2d_out [B][68][2],
+ *                        pts2d_out[p] = tr * pts2d_in[det < 0 ? flip_map[p] : p], then the pixel -> [-1,1] map when N > 0,
+ *                      with the x / y arithmetic of the 3-D field: for equal inputs x, y of pts2d_out are BITWISE x, y of
+ *                      pts_out.  Both pointers null: no work, and every other output is bitwise ttk_affine_labels' (one
+ *                      kernel serves both entry points).  pts2d_in / pts2d_out follow the aliasing rule of pts_in / pts_out.
  * ------------------------------------------------------------------------------------------- */
 int ttk_view_roi(const float* face_roi, const float* scales, const float* translations,
                  float beyond_border_shift, int B, int* view_roi, ttk_stream_t stream);
@@ -700,6 +707,9 @@ int ttk_area_crop(const void* src, int src_is_u8, int B, int Hs, int Ws, const f
                   int N, float mul, float add, ttk_stream_t stream);
 int ttk_affine_labels(const float* tr, int B, int N, float* coord, float* pose, float* roi,
                       const float* pts_in, float* pts_out, ttk_stream_t stream);
+int ttk_affine_labels2d(const float* tr, int B, int N, float* coord, float* pose, float* roi,
+                        const float* pts_in, float* pts_out, const float* pts2d_in, float* pts2d_out,
+                        ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Streaming probe (measurement infrastructure: bench.py `copy_probe`, tools/stream_sweep.py; no reference counterpart).

@@ -9,7 +9,7 @@
 //                contraction) in the reference's order; rintf = round-half-to-even like torch.round.
 //   roi -> tr  : center_rotation(angle) @ range_remap(view_roi -> [0,N]^2)            (:159-177)
 //   warp       : out[b,0,i,j] = bilinear(src_b, tr^-1 (j+.5, i+.5) - .5) * mul + add   (gather-bound)
-//   labels     : coord / pose / roi / pt3d_68 under tr, then under the [0,N] -> [-1,1] normalisation
+//   labels     : coord / pose / roi / pt3d_68 / pt2d_68 under tr, then under the [0,N] -> [-1,1] normalisation
 #include "head_math.h"
 #include "ttk_common.h"
 
@@ -92,9 +92,10 @@ struct Aff {
 };
 
 // labels of one sample under `m` (tensors/affinetrafo.py: transform_coord :107-114, transform_rot :117-148,
-// transform_roi :91-104, transform_points/keypoints :37-88).  pts_in/pts_out may alias only if det >= 0.
+// transform_roi :91-104, transform_points/keypoints :37-88).  pts_in/pts_out may alias only if det >= 0; likewise p2_in/p2_out, the
+// 2-D landmark field [68][2] (transform_points :51-52, transform_keypoints :70-71: the same map and flip map without a depth).
 __device__ void labels_under(const Aff m, float* coord, float* pose, float* roi, const float* pts_in, float* pts_out,
-                             int lane) {
+                             const float* p2_in, float* p2_out, int lane) {
   const float det = m.det();
   if (lane == 0) {
     if (coord) {
@@ -131,11 +132,20 @@ __device__ void labels_under(const Aff m, float* coord, float* pose, float* roi,
       pts_out[3 * p + 2] = zs * z;
     }
   }
+  if (p2_in) {
+    for (int p = lane; p < 68; p += 64) {
+      const int q = det < 0.f ? kFlipMap[p] : p;
+      const float x = p2_in[2 * q], y = p2_in[2 * q + 1];  // x / y as the 3-D field writes them: bitwise its x / y for equal inputs
+      p2_out[2 * p] = m.a * x + m.b * y + m.tx;
+      p2_out[2 * p + 1] = m.c * x + m.d * y + m.ty;
+    }
+  }
 }
 
 // one wave per sample: labels under tr[b], then (N > 0) under the pixel -> [-1,1] normalisation
 __global__ void __launch_bounds__(kWave) affine_labels_k(const float* __restrict__ tr, int B, int N, float* coord, float* pose,
-                                                          float* roi, const float* pts_in, float* pts_out) {
+                                                          float* roi, const float* pts_in, float* pts_out,
+                                                          const float* p2_in, float* p2_out) {
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= B) return;
   const float* t = tr + 6 * b;
@@ -144,11 +154,13 @@ __global__ void __launch_bounds__(kWave) affine_labels_k(const float* __restrict
   float* r = roi ? roi + 4 * b : nullptr;
   const float* pi = pts_in ? pts_in + (size_t)b * 204 : nullptr;
   float* po = pts_out ? pts_out + (size_t)b * 204 : nullptr;
-  labels_under(Aff{t[0], t[1], t[2], t[3], t[4], t[5]}, c, q, r, pi, po, lane);
+  const float* p2i = p2_in ? p2_in + (size_t)b * 136 : nullptr;
+  float* p2o = p2_out ? p2_out + (size_t)b * 136 : nullptr;
+  labels_under(Aff{t[0], t[1], t[2], t[3], t[4], t[5]}, c, q, r, pi, po, p2i, p2o, lane);
   if (N > 0) {
     __syncthreads();
     const float s = 2.f / (float)N;
-    labels_under(Aff{s, 0.f, -1.f, 0.f, s, -1.f}, c, q, r, po, po, lane);
+    labels_under(Aff{s, 0.f, -1.f, 0.f, s, -1.f}, c, q, r, po, po, p2o, p2o, lane);
   }
 }
 
@@ -189,8 +201,20 @@ int ttk_affine_labels(const float* tr, int B, int N, float* coord, float* pose, 
                       ttk_stream_t stream) {
   TTK_REQUIRE(tr && B > 0, "affine_labels: bad arguments");
   TTK_REQUIRE((pts_in == nullptr) == (pts_out == nullptr) && pts_in != pts_out || !pts_in, "affine_labels: pts_in/pts_out must be two distinct buffers");
-  hipLaunchKernelGGL(affine_labels_k, dim3(B), dim3(kWave), 0, (hipStream_t)stream, tr, B, N, coord, pose, roi, pts_in, pts_out);
+  hipLaunchKernelGGL(affine_labels_k, dim3(B), dim3(kWave), 0, (hipStream_t)stream, tr, B, N, coord, pose, roi, pts_in, pts_out,
+                     (const float*)nullptr, (float*)nullptr);
   TTK_LAUNCH_CHECK("affine_labels");
+}
+
+int ttk_affine_labels2d(const float* tr, int B, int N, float* coord, float* pose, float* roi, const float* pts_in, float* pts_out,
+                        const float* pts2d_in, float* pts2d_out, ttk_stream_t stream) {
+  TTK_REQUIRE(tr && B > 0, "affine_labels2d: bad arguments");
+  TTK_REQUIRE((pts_in == nullptr) == (pts_out == nullptr) && pts_in != pts_out || !pts_in, "affine_labels2d: pts_in/pts_out must be two distinct buffers");
+  TTK_REQUIRE((pts2d_in == nullptr) == (pts2d_out == nullptr) && pts2d_in != pts2d_out || !pts2d_in,
+              "affine_labels2d: pts2d_in/pts2d_out must be two distinct buffers");
+  hipLaunchKernelGGL(affine_labels_k, dim3(B), dim3(kWave), 0, (hipStream_t)stream, tr, B, N, coord, pose, roi, pts_in, pts_out,
+                     pts2d_in, pts2d_out);
+  TTK_LAUNCH_CHECK("affine_labels2d");
 }
 
 }  // extern "C"

@@ -213,7 +213,8 @@ def make_parser():
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--allow-landmark-roi-fallback", action="store_true", default=False,
                     help="without the BFM head-mesh blob: evaluate the (H_roi) configurations with the landmark extent (F_roi) instead of failing")
-    ap.add_argument("--ds", type=str, default="aflw2k3d", help="validation sets joined by '+', or paths of .npz files")
+    ap.add_argument("--ds", type=str, default="aflw2k3d", help="validation sets joined by '+' (trackertraincode.pipelines._VALIDATION_SHARDS: aflw2k3d, biwi, repro_300_wlp, ..., and the index subsets "
+                    "panoptic - CMU Panoptic's 1024 held-out frames - and replicantface-train), or paths of .npz files")
     ap.add_argument("--resample", default="bilinear", choices=["bilinear", "area"],
                     help="the crop's resampler: bilinear | area (the reference's anti-aliased crop; evaluate a network as it was trained)")
     ap.add_argument("--datadir", type=str, default=None, help="directory of the converted shards (default $DATADIR)")

@@ -153,7 +153,11 @@ def make_parser():
     p.add_argument("--batchsize", type=int, default=64)
     p.add_argument("--lr", type=float, default=1.0e-3)
     p.add_argument("--epochs", type=int, default=200)
-    p.add_argument("--ds", type=str, default="synthetic")
+    p.add_argument("--ds", type=str, default="synthetic",
+                   help="synthetic (seeded crops, the default) | <name>[:<weight>]+<name>[:<weight>]+... over the converted shards under $DATADIR: "
+                   "repro_300_wlp, repro_300_wlp_woextra, 300wlp (at most one of the three), wflw_lp, lapa_megaface_lp, replicantface, biwi, aflw2k, "
+                   "synface (landmarks only, 2.5D), panoptic (pose only; its 1024 validation frames are held out).  wider is refused (face "
+                   "detection).  E.g. repro_300_wlp+lapa_megaface_lp+wflw_lp+synface, or 300wlp:92+synface:8")
     p.add_argument("--with-swa", action="store_true", default=False, dest="swa")
     p.add_argument("--outdir", type=str, default=join(dirname(__file__), "..", "model_files"))
     p.add_argument("--ds-weighting", action="store_false", default=True, dest="ds_weight_are_sampling_frequencies")

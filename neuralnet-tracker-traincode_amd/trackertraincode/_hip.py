@@ -101,6 +101,7 @@ _SIGNATURES = {
     "ttk_affine_warp": [_P, _I, _I, _I, _I, _P, _P, _I, _F, _F],
     "ttk_area_crop": [_P, _I, _I, _I, _I, _P, _P, _I, _F, _F],
     "ttk_affine_labels": [_P, _I, _I, _P, _P, _P, _P, _P],
+    "ttk_affine_labels2d": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "ttk_intensity_augment": [_P, _P, _P, _P, _I, _I, _I, _F],
     "ttk_clip_adam": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P],
     "ttk_stream_probe": [_P, _P, _P, _L, _I, _I, _I, _I, _L, _I, _I, _I],
@@ -128,7 +129,7 @@ _SIGNATURES = {
     "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 
 # Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the

@@ -34,7 +34,7 @@ from .batch import Batch, Metadata
 from .randomized import PseudoRandomChoices
 
 _CATEGORIES = {"image": FieldCategory.image, "coord": FieldCategory.xys, "pose": FieldCategory.quat, "roi": FieldCategory.roi,
-               "pt3d_68": FieldCategory.points}
+               "pt3d_68": FieldCategory.points, "pt2d_68": FieldCategory.points}
 
 
 @dataclasses.dataclass

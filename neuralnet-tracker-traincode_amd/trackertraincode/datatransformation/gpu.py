@@ -24,7 +24,7 @@ def check_resample(resample) -> str:
 
 class GpuFocusRoiAugment:
     """batch fields used: image u8/f32 [B,1,Hs,Ws] (grey levels 0..255), roi [B,4] (pixels), and - if present -
-    coord [B,3], pose [B,4], pt3d_68 [B,68,3].  Returns a new Batch with image f32 [B,1,N,N] = crop/256 - 0.5
+    coord [B,3], pose [B,4], pt3d_68 [B,68,3], pt2d_68 [B,68,2].  Returns a new Batch with image f32 [B,1,N,N] = crop/256 - 0.5
     and labels in the crop's [-1,1] coordinates; other fields pass through."""
 
     def __init__(self, new_size=129, rotation_aug_angle=30.0, extension_factor=1.1, beyond_border_shift=0.3, whiten=True,
@@ -38,7 +38,8 @@ class GpuFocusRoiAugment:
         flip_rot_p: the reference's `horizontal_flip_and_rot_90(p_rot)` behind the crop (pipelines.py:373-377, batch/geometric.py:234-267):
         every sample is mirrored with probability 1/2 and turned by +-90 degrees with probability p_rot / 2 each; None = off (the eval
         stage).  roi_from_landmarks: `roi_override="landmarks"` (pipelines.py:343-350, batch/misc.py:9-31): the face box the crop is taken
-        around AND the box label of the crop are the xy extent of pt3d_68 (samples without landmarks keep their stored box)."""
+        around AND the box label of the crop are the xy extent of pt3d_68 (samples without landmarks keep their stored box; like the
+        reference's PutRoiFromLandmarks the rule reads pt3d_68 only - a set that carries just pt2d_68 keeps its stored box too)."""
         self.new_size = int(new_size)
         self.beyond_border_shift = float(beyond_border_shift)
         self.make_params = make_params or MakeRoiRandomizationParameters(rotation_aug_angle, extension_factor)
@@ -121,7 +122,15 @@ class GpuFocusRoiAugment:
         new_roi = roi.clone()
         pts_in = f32(batch["pt3d_68"]) if "pt3d_68" in batch else None
         pts_out = torch.empty_like(pts_in) if pts_in is not None else None
-        L.call("ttk_affine_labels", _p(tr), B, self.new_size, _p(coord), _p(pose), _p(new_roi), _p(pts_in), _p(pts_out))
+        pts2_in = f32(batch["pt2d_68"]) if "pt2d_68" in batch else None
+        if pts2_in is None:
+            L.call("ttk_affine_labels", _p(tr), B, self.new_size, _p(coord), _p(pose), _p(new_roi), _p(pts_in), _p(pts_out))
+        else:  # the 2-D landmarks under the same (composed) transform, flip map included (reference tensors/affinetrafo.py:51-52, 70-71)
+            if tuple(pts2_in.shape) != (B, 68, 2):
+                raise ValueError(f"pt2d_68: expected [{B}, 68, 2], got {tuple(pts2_in.shape)}")
+            pts2_out = torch.empty_like(pts2_in)
+            L.call("ttk_affine_labels2d", _p(tr), B, self.new_size, _p(coord), _p(pose), _p(new_roi), _p(pts_in), _p(pts_out), _p(pts2_in), _p(pts2_out))
+            out["pt2d_68"] = pts2_out
         if self.roi_from_landmarks and pts_out is not None:  # PutRoiFromLandmarks behind the crop: the box label = extent of the crop's landmarks
             xy = pts_out[..., :2]
             new_roi = torch.cat((xy.amin(dim=-2), xy.amax(dim=-2)), dim=-1).contiguous()

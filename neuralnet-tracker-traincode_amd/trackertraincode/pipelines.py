@@ -153,8 +153,25 @@ class SyntheticPoseLoader:
             yield batches[0] if self._single else batches
 
 
-# The pose datasets of the reference that carry what the pose-estimator step trains on (pipelines.py:120-300, 399-453): file (as an .npz
-# shard converted by oracle/tools/h5_to_npz.py), task Tag, default sampling weight, and the frame range of the train split.
+def panoptic_test_indices(n: int) -> np.ndarray:
+    """The 1024 validation frames of CMU Panoptic, in the order `choice` drew them (reference :137)."""
+    return np.random.RandomState(seed=1234567).choice(n, 1024, replace=False)
+
+
+def panoptic_train_indices(n: int) -> np.ndarray:
+    """Every other frame, ascending (reference :138)."""
+    return np.setdiff1d(np.arange(n), panoptic_test_indices(n))
+
+
+def replicantface_train_subset_indices(n: int) -> np.ndarray:
+    """The 1000 frames of the Replicant-Face TRAIN file that the evaluation script looks at (reference :593-595; drawn with replacement and never
+    the last frame, as there)."""
+    return np.random.default_rng(seed=42).integers(0, n - 1, size=1000)
+
+
+# The datasets of the reference that carry what the pose-estimator step trains on (pipelines.py:72-300, 399-453): file (as an .npz
+# shard converted by oracle/tools/h5_to_npz.py), task Tag, default sampling weight, and the train split: None (every frame), a frame range
+# (lo, hi), or a function of the frame count that returns the frames' indices.
 _POSE_SHARDS = {
     Id.REPO_300WLP: ("reproduction_300wlp-v12", Tag.POSE_WITH_LANDMARKS, 60_000.0, None),
     Id.REPO_300WLP_WO_EXTRA: ("reproduction_300wlp_simple", Tag.POSE_WITH_LANDMARKS, 60_000.0, None),
@@ -164,15 +181,23 @@ _POSE_SHARDS = {
     Id.REPLICANT_FACE: ("replicant-face-v4-wider-100k", Tag.POSE_WITH_LMKS_NO_SHAPE_PARAMS, 10_000.0, None),
     Id.BIWI: ("biwi-v3", Tag.ONLY_POSE, 1_000.0, None),
     Id.AFLW2k3d: ("aflw2k", Tag.POSE_WITH_LANDMARKS, 1_000.0, (400, None)),  # frames 400.. train, 0..399 test (:266-271)
+    # landmark-only / pose-only sets (:77-156, 399-431).  Face Synthetics stores 2-D landmarks as pt3d_68 with a zero z ("2.5D": its criterion
+    # reads x and y only); the three ONLY_LANDMARKS_2D sets carry pt2d_68 and have no criterion in the training script (API only).
+    Id.SYNFACE: ("microsoft_synface_100000-v1.1", Tag.ONLY_LANDMARKS_25D, 10_000.0, None),
+    Id.PANOPTIC_CMU: ("panoptic-v2", Tag.ONLY_POSE, 20_000.0, panoptic_train_indices),
+    Id._300VW: ("300vw", Tag.ONLY_LANDMARKS_2D, 5_000.0, None),
+    Id.LAPA: ("lapa", Tag.ONLY_LANDMARKS_2D, 20_000.0, None),
+    Id.WFLW_RELABEL: ("wflw_train", Tag.ONLY_LANDMARKS_2D, 10_000.0, None),
 }
+# `coord_convention_id` of a shard's frames where it is not 0 (reference :135: Panoptic's poses follow the other head-centre convention)
+_COORD_CONVENTION = {"panoptic-v2": 1}
 _TEST_SHARD = ("aflw2k", Tag.POSE_WITH_LANDMARKS, (0, 400))  # the validation set of every run (:455-456)
 
 
 # ---------------------------------------------------------------------------------------------
 # validation sets of the evaluation script (reference :170-271, 557-636)
 # ---------------------------------------------------------------------------------------------
-# name -> (shard file, "filter").  The sets the reference builds from pose datasets with stored frames; the panoptic / replicant-face
-# variants with a train/test split or a random subset are not listed.
+# name -> (shard file, "filter": None, a rule name, or a function of the frame count that returns the frames' indices in serving order).
 _VALIDATION_SHARDS = {
     "aflw2k3d": ("aflw2k", "no_extreme_poses"),
     "aflw2k3d_closedeyes": ("aflw2k3d-closedeyes", "no_extreme_poses"),
@@ -185,6 +210,8 @@ _VALIDATION_SHARDS = {
     "lapa_megaface_lp": ("lapa-megaface-augmented-v2", None),
     "replicantface": ("replicant-face-v4-eval-10k", None),
     "replicantface-stability": ("replicant-face-stability-test-wider", None),
+    "panoptic": ("panoptic-v2", panoptic_test_indices),
+    "replicantface-train": ("replicant-face-v4-wider-100k", replicantface_train_subset_indices),
 }
 # frames of AFLW2000-3D's first 400 (the test split) with strong facial expressions (reference :208-263)
 _AFLW2K_GRIMACES = (39, 236, 0, 129, 164, 356, 359, 256, 136, 375, 226, 392, 119, 366, 293, 56, 305, 303, 397, 10, 11, 96, 173, 124, 115, 153, 337,
@@ -202,10 +229,12 @@ def indices_without_extreme_poses(quats, coords):
 
 class ValidationSamples:
     """Single labelled frames for `eval.Predictor.evaluate` (the reference's SampleBySampleLoader over make_validation_dataset): dicts with
-    "image" (uint8 [H, W], unpadded), the labels as CPU tensors, "index" and - where the file knows it - "individual"."""
+    "image" (uint8 [H, W], unpadded), the labels as CPU tensors, "index" and - where the file knows it - "individual"; sets whose poses
+    follow another head-centre convention than 0 also carry "coord_convention_id"."""
 
-    def __init__(self, shard: dict, indices, put_roi):
+    def __init__(self, shard: dict, indices, put_roi, coord_convention_id: int = 0):
         self._shard, self._indices, self._put_roi = shard, np.asarray(indices), put_roi
+        self.coord_convention_id = int(coord_convention_id)
 
     def __len__(self):
         return len(self._indices)
@@ -216,6 +245,8 @@ class ValidationSamples:
             s = {k: torch.from_numpy(np.asarray(v[i])) for k, v in self._shard.items() if k not in ("image", "image_size")}
             s["image"] = torch.from_numpy(self._shard["image"][i, 0, :h, :w])
             s["index"] = torch.tensor(int(i), dtype=torch.int32)
+            if self.coord_convention_id:
+                s["coord_convention_id"] = torch.tensor(self.coord_convention_id, dtype=torch.int32)
             yield self._put_roi(s)
 
 
@@ -243,11 +274,15 @@ def make_validation_dataset(name, order=None, use_head_roi=True, datadir=None, h
         indices = indices_without_extreme_poses(shard["pose"], shard["coord"])
     elif rule == "grimaces":
         indices = np.asarray(_AFLW2K_GRIMACES)
+    elif callable(rule):
+        indices = np.asarray(rule(n))
     else:
         indices = np.arange(n)
     if order is not None:
         indices = indices[np.asarray(order)]
-    return ValidationSamples(shard, indices, PutRoiFromLandmarks(extend_to_forehead=use_head_roi, headmodel=headmodel))
+    if "pt3d_68" not in shard:
+        use_head_roi = False  # PutRoiFromLandmarks leaves a sample without pt3d_68 alone (batch/misc.py:28-31): no head mesh is needed for such a set
+    return ValidationSamples(shard, indices, PutRoiFromLandmarks(extend_to_forehead=use_head_roi, headmodel=headmodel), _COORD_CONVENTION.get(fname, 0))
 
 
 def make_validation_loader(name, order=None, use_head_roi=True, return_single_samples=True, datadir=None, headmodel=None):
@@ -261,6 +296,25 @@ def _slice_frames(frames, lo, hi):
     from .datasets.resident import ResidentFrames
 
     return ResidentFrames(frames.tag, {k: v[lo:hi] for k, v in frames.fields.items()})
+
+
+def _select_frames(frames, indices):
+    """The frames `indices` (any order, repeats allowed) as a ResidentFrames of their own, on the device or in (pinned) host memory as
+    `frames` is.  Gathered ONCE, here: the loaders draw from the result as from any other set, nothing is added per step."""
+    from .datasets.resident import ResidentFrames
+
+    idx = np.asarray(indices).astype(np.int64).reshape(-1)
+    if len(idx) and (idx.min() < 0 or idx.max() >= len(frames)):
+        raise IndexError(f"_select_frames: indices outside 0..{len(frames) - 1}")
+    sel = torch.from_numpy(idx)
+    out = {}
+    for k, v in frames.fields.items():
+        if v.is_cuda:
+            out[k] = v.index_select(0, sel.to(v.device))
+        else:
+            t = torch.from_numpy(np.take(v.numpy(), idx, axis=0))  # (numpy.take: torch.index_select on uint8 host tensors is 30 x slower)
+            out[k] = t.pin_memory() if v.is_pinned() else t
+    return ResidentFrames(frames.tag, out)
 
 
 def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights=None, use_weights_as_sampling_frequency=True,
@@ -277,6 +331,9 @@ def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights
         the intensity augmentation run on the GPU (datasets/resident.py).  The test loader is the deterministic crop of the first 400
         AFLW2000-3D frames, as in the reference.  Behind the crop every sample is mirrored with probability 1/2 and turned by +-90
         degrees with probability 0.5 % each (`horizontal_flip_and_rot_90(0.01)`, :373-377), composed into the crop's warp.
+        Every `Id` but `WIDER` (face detection) is served: the pose sets, Face Synthetics (`SYNFACE`, landmarks only), CMU Panoptic
+        (`PANOPTIC_CMU`, pose only, coord convention 1, without its 1024 validation frames) and the 2-D landmark sets `_300VW`, `LAPA`,
+        `WFLW_RELABEL` (`pt2d_68`; the training script has no criterion for their Tag).
         `roi_override`: "original" (stored face boxes, crop enlargement 1.1) or "landmarks" (boxes = xy extent of pt3d_68 in front of and
         behind the crop, enlargement 1.2; :329-350) or "extent_to_forehead" (boxes = xy extent of the posed BFM head mesh in front of the
         crop only, enlargement 1.1; :351-356 - computed once per resident frame set, since they depend on the labels alone).  The last one
@@ -320,8 +377,9 @@ def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights
         raise RuntimeError("make_pose_estimation_loaders: set $DATADIR (or pass datadir=) to the directory of converted .npz shards")
     unsupported = [d for d in datasets if d not in _POSE_SHARDS]
     if unsupported:
-        raise NotImplementedError(f"datasets {unsupported}: landmark-only / face-detection / segmentation sets are outside the pose-estimator "
-                                  f"path this package implements (supported: {sorted(d.name for d in _POSE_SHARDS)})")
+        why = ("Id.WIDER is a FACE_DETECTION set: its samples train the `hasface` head, which NetworkWithPointHead(enable_face_detector=True) "
+               "would provide - and that switch is refused (the training script never sets it).  " if Id.WIDER in unsupported else "")
+        raise NotImplementedError(f"datasets {unsupported}: {why}Supported: {sorted(d.name for d in _POSE_SHARDS)}")
     if len([d for d in datasets if d in (Id._300WLP, Id.REPO_300WLP, Id.REPO_300WLP_WO_EXTRA)]) > 1:
         raise ValueError("at most one 300W-LP variant (reference :435-438)")
     if frames_on not in ("auto", "device", "host"):
@@ -332,13 +390,16 @@ def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights
         budget = torch.cuda.get_device_properties(device).total_memory // 2 if str(device).startswith("cuda") else 0
     on_device_bytes = [0]
 
-    def shard(name, tag):
+    def shard(name, tag, indices_of=None):
         path = os.path.join(datadir, name + ".npz")
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found: convert {name}.h5 with `/opt/conda/bin/python3.9 oracle/tools/h5_to_npz.py --dataset "
                                     f"{name}.h5 {path}` (h5py lives in the build container's conda interpreter only)")
-        if path not in cache:
-            frames = load_resident_frames(path, tag, "cpu")
+        key = path if indices_of is None else (path, indices_of)
+        if key not in cache:
+            frames = load_resident_frames(path, tag, "cpu", coord_convention_id=_COORD_CONVENTION.get(name, 0))
+            if indices_of is not None:  # an index subset is taken BEFORE the frames are placed: only its frames occupy HBM / pinned memory
+                frames = _select_frames(frames, indices_of(len(frames)))
             if head_roi is not None and "pt3d_68" in frames.fields and str(device).startswith("cuda"):
                 # the forehead box is the extent of the posed head MESH (tens of thousands of vertices per frame): computed on the GPU from
                 # the labels alone, BEFORE the frames are placed - on host-placed sets it would otherwise run on the CPU for every frame
@@ -349,18 +410,21 @@ def make_pose_estimation_loaders(inputsize, batchsize, datasets, dataset_weights
                 head_roi(frames.fields)  # frames with landmarks get the forehead box; the others keep their stored one
             if frames_on == "device" or (frames_on == "auto" and on_device_bytes[0] + frames.nbytes() <= budget):
                 on_device_bytes[0] += frames.nbytes()
-                cache[path] = frames.to(device)
+                cache[key] = frames.to(device)
             else:  # beyond the HBM budget (or asked for): pinned host memory, streamed per step
-                cache[path] = frames.to_host()
-        return cache[path]
+                cache[key] = frames.to_host()
+        return cache[key]
 
     dataset_weights = dataset_weights or {}
     train_sets, weights = [], []
     for d in datasets:
         name, tag, default_w, rng = _POSE_SHARDS[d]
-        frames = shard(name, tag)
-        if rng is not None:
-            frames = _slice_frames(frames, rng[0], rng[1])
+        if callable(rng):
+            frames = shard(name, tag, rng)
+        else:
+            frames = shard(name, tag)
+            if rng is not None:
+                frames = _slice_frames(frames, rng[0], rng[1])
         train_sets.append(frames)
         weights.append(float(dataset_weights.get(d, default_w)))
     total = sum(len(t) for t in train_sets)
