@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 33
+#define TTK_ABI_VERSION 34
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -388,6 +388,95 @@ int ttk_bc_dw_bwd_data(const void* g_dw, const void* y_dw, const float* bn_dw, c
 int ttk_bc_bn_bwd_finalize_fold(float* part, int part_rows, int C, int64_t count, const float* gamma, float* bn, float* dgamma, float* dbeta,
                                 int accumulate, const float* fold_partial, int fold_rows, int64_t fold_n, float* fold_out, int fold_accumulate,
                                 ttk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The MobileNet backbone as ONE call per direction (ABI 34; csrc/mobilenet_seq.hip: host code only, no kernel of its own).
+ * Reference: everything MobileNet.forward does up to the pooled features (backbones/mobilenet_v1.py:96-189) and its autograd
+ * backward.  The two calls issue the per-kernel entry points declared above, in the order and with the arguments of the shipped
+ * Python host in its product configuration (backbones/mobilenet_v1.py, backbones/_mobilenet_bc.py): the raw
+ * residual operand behind the blocks dw3_1 and dw4_1 (block indices 2 and 4 of the table, where they head a chain of residual
+ * blocks on the tuned kernels), the fused backward of the early pointwise layers, the depthwise weight-gradient rows folded in
+ * the launch that finalises the producer's BatchNorm backward, the tuned / any-channel-count choice per layer (tuned: channel
+ * counts that are powers of two in 32..1024), statistics pivots = the running means.  Not reproduced: a second stream for the
+ * weight gradients and the host's experiment switches.
+ *
+ * A binder fills a caller-owned plan once per shape (plain data: no handle, no allocation), allocates the two workspaces and the
+ * gradient arena, and calls forward / backward.  The library allocates nothing, creates no stream or event and never
+ * synchronises - both calls can be captured in a hipGraph.  Zero fills (the BatchNorm constant blocks, whose TTK_BN_AUX row must
+ * start at zero, and the gradient arena, which the weight-gradient kernels add to) are memset nodes on the caller's stream.
+ *
+ * Workspaces.  ttk_mobilenet_plan_init cuts both into sub-buffers, 256-byte aligned and disjoint: buf_off / buf_bytes [0] =
+ * forward, [1] = backward.  The FORWARD workspace holds what backward reads again and must stay untouched between the two calls:
+ * the scratch rows of partial sums (`part`), the BatchNorm constant blocks, the prepared weight operands, every raw conv output
+ * and every stored block input.  The BACKWARD workspace holds the gradient activations and the weight-gradient scratch.  The
+ * gradient of a block's output and of its input alternate between two buffers (i_g), the gradient behind the pointwise layer
+ * and behind a blur have one buffer each (i_gdw, i_gt): buffers that are live at the same time are disjoint, a buffer is written
+ * again only by a launch behind its last reader on the same stream.
+ *
+ * Parameters: `params` = 3 + 6 * nblocks device pointers - stem weight, gamma, beta, then per block depthwise weight, gamma, beta,
+ * pointwise weight, gamma, beta (the reference's tensors as they are).  `buffers` = 3 * (1 + 2 * nblocks) pointers - per
+ * BatchNorm running_mean, running_var, num_batches_tracked (int64, nullable) in the same order.  `blur_kernels` = nblocks
+ * pointers ([Cin][1][3][3] depthwise form of the BlurPool2D kernel; read where the plan's blur mask is set; the array may be
+ * NULL for a plan without blur).  The gradient arena holds every parameter gradient in parameter order, each padded to a
+ * multiple of 64 floats (plan->arena_floats in all); backward zeroes and fills it.
+ * on_ready (nullable) is called on the calling thread, synchronously, right after the launches that finalise parameters
+ * [first_param, last_param) have been enqueued: one call per block from the last block to the first, then (0, 3) for the stem -
+ * a data-parallel binder enqueues its all-reduce of that slice of the arena on the same stream from inside the callback.
+ * Every argument is checked before the first launch; a refused call has launched nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define TTK_MOBILENET_MAX_BLOCKS 16
+#define TTK_MOBILENET_MAX_BUFFERS 96
+enum { TTK_MOBILENET_TRAIN = 0,    /* batch statistics, running statistics updated                                    */
+       TTK_MOBILENET_FROZEN = 1,   /* eval-mode statistics, convolutions trainable (backward: fixed affine BatchNorm)  */
+       TTK_MOBILENET_EVAL = 2 };   /* forward only                                                                    */
+enum { TTK_MOBILENET_FP32 = 0, TTK_MOBILENET_BF16_COMPUTE = 1 };
+typedef struct ttk_mobilenet_plan {
+  /* what ttk_mobilenet_plan_init was given */
+  int B, H, W, c0, nblocks, mode, precision, deterministic;
+  int cin[TTK_MOBILENET_MAX_BLOCKS], cout[TTK_MOBILENET_MAX_BLOCKS], stride[TTK_MOBILENET_MAX_BLOCKS], blur[TTK_MOBILENET_MAX_BLOCKS];
+  /* derived by it (read-only for the caller; forward / backward refuse a plan whose fields above were changed afterwards).  A binder needs
+   * ws_bytes (or the two size calls), arena_floats, nparams / nbuffers and launches; the sub-buffer tables are published so that tools and
+   * tests can check the cut - their content may change with TTK_ABI_VERSION like everything else here. */
+  uint64_t check;
+  int nparams, nbuffers;
+  int launches[2];                  /* entry-point calls of forward [0] / backward [1] */
+  int nbuf[2];                      /* sub-buffers of the forward [0] / backward [1] workspace */
+  uint64_t ws_bytes[2];
+  uint64_t arena_floats;
+  uint64_t buf_off[2][TTK_MOBILENET_MAX_BUFFERS], buf_bytes[2][TTK_MOBILENET_MAX_BUFFERS];
+  /* indices into table [0]; -1 = the plan has no such buffer */
+  int i_part, i_bn, i_prep, i_y0;
+  int i_ain[TTK_MOBILENET_MAX_BLOCKS], i_t[TTK_MOBILENET_MAX_BLOCKS], i_idbn[TTK_MOBILENET_MAX_BLOCKS], i_ydw[TTK_MOBILENET_MAX_BLOCKS],
+      i_ypw[TTK_MOBILENET_MAX_BLOCKS];
+  uint64_t prep_off[TTK_MOBILENET_MAX_BLOCKS], prep_bytes[TTK_MOBILENET_MAX_BLOCKS]; /* within buffer i_prep; 0 bytes: raw weights */
+  /* indices into table [1] */
+  int i_g[2], i_gdw, i_gt, i_wg, i_pw, i_dwrows, i_any;
+} ttk_mobilenet_plan;
+typedef void (*ttk_mobilenet_ready_fn)(void* user, int first_param, int last_param);
+
+/* sizeof(ttk_mobilenet_plan) as the library was built: a binder that mirrors the struct in another language checks its own size against it
+ * (the shipped ctypes host does when it loads the library). */
+size_t ttk_mobilenet_plan_bytes(void);
+/* Fills *plan; all validation happens here (channel domains per kernel family, 32-bit indexing limits, bf16-compute at any block
+ * table other than the reference's width 1.0).  0 = ok; on a refusal *plan is zeroed and every later call with it fails.
+ * The raw residual operand is a POSITIONAL rule: it applies at block indices 2 and 4 (dw3_1, dw4_1 of the reference's 13-block table and
+ * of its width-scaled forms, which is what the shipped host builds) where such a block heads a chain of residual blocks on the tuned
+ * kernels, whatever the table; at every other block the input of a residual block is stored.  Either form computes the same values. */
+int ttk_mobilenet_plan_init(ttk_mobilenet_plan* plan, int B, int H, int W, int c0, int nblocks, const int* cin, const int* cout,
+                            const int* stride, const int* blur, int mode, int precision, int deterministic);
+size_t ttk_mobilenet_forward_workspace_bytes(const ttk_mobilenet_plan* plan);  /* 0: not a valid plan */
+size_t ttk_mobilenet_backward_workspace_bytes(const ttk_mobilenet_plan* plan);
+int ttk_mobilenet_forward(const ttk_mobilenet_plan* plan, const float* x, const float* const* params, int nparams,
+                          void* const* buffers, int nbuffers, const float* const* blur_kernels, float momentum, float eps,
+                          void* workspace, size_t workspace_bytes, float* feat, ttk_stream_t stream);
+int ttk_mobilenet_backward(const ttk_mobilenet_plan* plan, const float* gfeat, const float* x, const float* const* params, int nparams,
+                           const float* const* blur_kernels, void* forward_workspace, size_t forward_workspace_bytes,
+                           void* backward_workspace, size_t backward_workspace_bytes, float* grad_arena, size_t arena_floats,
+                           ttk_mobilenet_ready_fn on_ready, void* user, ttk_stream_t stream);
+/* The plan's launch list: the names of the entry points forward (backward == 0) or backward issues, in order, separated by '\n',
+ * NUL-terminated.  Returns the number of names, or -1 (bad plan; `capacity` too small).  *needed (nullable) receives the bytes the list
+ * takes; names == NULL is a size query: nothing is written, no error is recorded, the number of names is returned. */
+int ttk_mobilenet_describe(const ttk_mobilenet_plan* plan, int backward, char* names, size_t capacity, size_t* needed);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense convolutions of the ResNet18 backbone variant (backbones/resnet.py:52-104; arithmetic =

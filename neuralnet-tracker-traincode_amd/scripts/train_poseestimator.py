@@ -175,6 +175,10 @@ def make_parser():
                    help="fp32 (the reference's precision) | bf16-compute (mobilenetv1): activations and their gradients bfloat16 in 64-channel blocks AND bf16 "
                    "operands of the pointwise convolutions (one MFMA product, fp32 accumulation; master weights, statistics and Adam fp32).  The "
                    "storage-only variants bf16 / bf16-all of earlier rounds are retired (they were slower than fp32): they raise, naming bf16-compute")
+    p.add_argument("--sequence", default="python", choices=["python", "native"],
+                   help="mobilenetv1: who issues the backbone's launches - python (one ctypes call and one allocation per launch) | native (one C call "
+                   "per direction, ttk_mobilenet_forward / ttk_mobilenet_backward: the same launches with less host time per eager step - data-parallel "
+                   "runs, which cannot replay a graph)")
     p.add_argument("--widen-factor", default=1.0, type=float, dest="widen_factor",
                    help="mobilenetv1: width multiplier of the backbone (the reference's MobileNet(widen_factor=...)): every channel count becomes "
                    "int(c * factor) and must be a multiple of 8 in 8..2048 - 0.25, 0.5, 0.75, 1.0, 1.5, 2.0; fp32 precision only")
@@ -208,6 +212,7 @@ def main():
     from trackertraincode.backbones import mobilenet_v1
 
     mobilenet_v1.set_activation_dtype(args.precision)
+    mobilenet_v1.set_sequence(args.sequence)
     world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
     # TTK_DRYRUN_SHARE_GPU=1: every rank on device 0 with gloo instead of RCCL - a dry run of the multi-rank wiring on a one-GPU box
     # (tests/test_train_script_dp_dryrun_gpu.py); RCCL needs one device per rank

@@ -129,7 +129,7 @@ _SIGNATURES = {
     "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 
 # Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the
@@ -139,6 +139,27 @@ BN_PIVOT = True
 
 def bn_pivot() -> bool:
     return BN_PIVOT
+
+
+MOBILENET_MAX_BLOCKS, MOBILENET_MAX_BUFFERS = 16, 96  # TTK_MOBILENET_MAX_BLOCKS, TTK_MOBILENET_MAX_BUFFERS
+MOBILENET_MODES = {"train": 0, "frozen": 1, "eval": 2}   # TTK_MOBILENET_TRAIN / _FROZEN / _EVAL
+MOBILENET_PRECISIONS = {"fp32": 0, "bf16-compute": 1}    # TTK_MOBILENET_FP32 / _BF16_COMPUTE
+
+
+class MobileNetPlan(ctypes.Structure):
+    """ttk_mobilenet_plan (include/ttk.h): the caller-owned plan of the backbone-level calls ttk_mobilenet_forward / _backward."""
+    _fields_ = [(n, c_int) for n in ("B", "H", "W", "c0", "nblocks", "mode", "precision", "deterministic")] + \
+               [(n, c_int * MOBILENET_MAX_BLOCKS) for n in ("cin", "cout", "stride", "blur")] + \
+               [("check", ctypes.c_uint64), ("nparams", c_int), ("nbuffers", c_int), ("launches", c_int * 2), ("nbuf", c_int * 2),
+                ("ws_bytes", ctypes.c_uint64 * 2), ("arena_floats", ctypes.c_uint64),
+                ("buf_off", (ctypes.c_uint64 * MOBILENET_MAX_BUFFERS) * 2), ("buf_bytes", (ctypes.c_uint64 * MOBILENET_MAX_BUFFERS) * 2)] + \
+               [(n, c_int) for n in ("i_part", "i_bn", "i_prep", "i_y0")] + \
+               [(n, c_int * MOBILENET_MAX_BLOCKS) for n in ("i_ain", "i_t", "i_idbn", "i_ydw", "i_ypw")] + \
+               [("prep_off", ctypes.c_uint64 * MOBILENET_MAX_BLOCKS), ("prep_bytes", ctypes.c_uint64 * MOBILENET_MAX_BLOCKS), ("i_g", c_int * 2)] + \
+               [(n, c_int) for n in ("i_gdw", "i_gt", "i_wg", "i_pw", "i_dwrows", "i_any")]
+
+
+MOBILENET_READY_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int)  # ttk_mobilenet_ready_fn
 
 
 class LossOp(ctypes.Structure):
@@ -205,6 +226,22 @@ class _Library:
         self.cdll.ttk_anyc_stem_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_stem_wgrad_scratch_bytes.restype = [c_int] * 4, ctypes.c_size_t
         self.cdll.ttk_anyc_dw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_dw_wgrad_scratch_bytes.restype = [c_int] * 4, ctypes.c_size_t
         self.cdll.ttk_anyc_pw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_pw_wgrad_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
+        PP = ctypes.POINTER(MobileNetPlan)
+        self.cdll.ttk_mobilenet_plan_init.argtypes = [PP] + [c_int] * 5 + [ctypes.POINTER(c_int)] * 4 + [c_int] * 3
+        self.cdll.ttk_mobilenet_plan_init.restype = c_int
+        for name in ("ttk_mobilenet_forward_workspace_bytes", "ttk_mobilenet_backward_workspace_bytes"):
+            getattr(self.cdll, name).argtypes, getattr(self.cdll, name).restype = [PP], ctypes.c_size_t
+        self.cdll.ttk_mobilenet_describe.argtypes = [PP, c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        self.cdll.ttk_mobilenet_describe.restype = c_int
+        self.cdll.ttk_mobilenet_plan_bytes.argtypes, self.cdll.ttk_mobilenet_plan_bytes.restype = [], ctypes.c_size_t
+        if self.cdll.ttk_mobilenet_plan_bytes() != ctypes.sizeof(MobileNetPlan):
+            raise RuntimeError(f"ttk_mobilenet_plan is {self.cdll.ttk_mobilenet_plan_bytes()} bytes in libttk_hip.so, {ctypes.sizeof(MobileNetPlan)} in "
+                               "_hip.MobileNetPlan: the two definitions differ")
+        self.cdll.ttk_mobilenet_forward.argtypes = [PP, _P, _P, _I, _P, _I, _P, _F, _F, _P, ctypes.c_size_t, _P, _P]
+        self.cdll.ttk_mobilenet_forward.restype = c_int
+        self.cdll.ttk_mobilenet_backward.argtypes = [PP, _P, _P, _P, _I, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                     MOBILENET_READY_FN, _P, _P]
+        self.cdll.ttk_mobilenet_backward.restype = c_int
         self._fns = {}
         self._stale_reported = False
         for name, sig in _SIGNATURES.items():
@@ -271,6 +308,54 @@ class _Library:
             else:
                 sets = (ctypes.c_uint * len(chunk))(*[int(m) & 0xFFFFFFFF for m in tag_sets[lo:lo + LOSS_BATCH_MAX]])
                 self.call("ttk_loss_batch_rows", len(chunk), arr, sets, ptr(tag_code))
+
+    def _raise(self, name, rc):
+        msg = self.cdll.ttk_last_error_string().decode(errors="replace")
+        raise RuntimeError(f"{name} failed (code {rc}): {msg}")
+
+    @functools.lru_cache(maxsize=64)
+    def mobilenet_plan(self, B, H, W, c0, blocks, blur, mode, precision, deterministic) -> MobileNetPlan:
+        """ttk_mobilenet_plan_init: the plan of the backbone-level calls for one shape (cached: plain data, read-only afterwards).  `blocks`:
+        ((cin, cout, stride), ...); `blur`: one flag per block; `mode`: "train" | "frozen" | "eval"; `precision`: "fp32" | "bf16-compute".
+        A refusal (a channel count outside the kernels' domains, bf16-compute at another width, 32-bit limits) raises ValueError."""
+        n = len(blocks)
+        if n > MOBILENET_MAX_BLOCKS:
+            raise ValueError(f"the backbone-level calls take up to {MOBILENET_MAX_BLOCKS} blocks, got {n}")
+        plan = MobileNetPlan()
+        IA = c_int * n
+        rc = self.cdll.ttk_mobilenet_plan_init(ctypes.byref(plan), B, H, W, c0, n, IA(*[b[0] for b in blocks]), IA(*[b[1] for b in blocks]),
+                                               IA(*[b[2] for b in blocks]), IA(*[int(bool(f)) for f in blur]), MOBILENET_MODES[mode],
+                                               MOBILENET_PRECISIONS[precision], int(bool(deterministic)))
+        if rc != 0:
+            raise ValueError(self.cdll.ttk_last_error_string().decode(errors="replace"))
+        return plan
+
+    def mobilenet_describe(self, plan: MobileNetPlan, backward: bool) -> list[str]:
+        """ttk_mobilenet_describe: the entry points the plan's forward / backward issues, in order."""
+        need = ctypes.c_size_t(0)
+        if self.cdll.ttk_mobilenet_describe(ctypes.byref(plan), int(backward), None, 0, ctypes.byref(need)) < 0:  # (names == NULL: the size query)
+            self._raise("ttk_mobilenet_describe", -1)
+        buf = ctypes.create_string_buffer(max(1, need.value))
+        n = self.cdll.ttk_mobilenet_describe(ctypes.byref(plan), int(backward), buf, len(buf), None)
+        if n < 0:
+            self._raise("ttk_mobilenet_describe", n)
+        names = buf.value.decode().split("\n") if buf.value else []
+        assert len(names) == n, (len(names), n)
+        return names
+
+    def mobilenet_forward(self, plan, x, params, buffers, blur, momentum, eps, workspace, feat):
+        """ttk_mobilenet_forward on torch's current stream.  `params` / `buffers` / `blur`: ctypes arrays of device pointers (blur: or None)."""
+        rc = self.cdll.ttk_mobilenet_forward(ctypes.byref(plan), x.data_ptr(), params, len(params), buffers, len(buffers), blur, momentum, eps,
+                                             workspace.data_ptr(), workspace.numel(), feat.data_ptr(), _raw_stream(_cur_device()))
+        if rc != 0:
+            self._raise("ttk_mobilenet_forward", rc)
+
+    def mobilenet_backward(self, plan, gfeat, x, params, blur, fws, bws, arena, on_ready):
+        rc = self.cdll.ttk_mobilenet_backward(ctypes.byref(plan), gfeat.data_ptr(), x.data_ptr(), params, len(params), blur, fws.data_ptr(), fws.numel(),
+                                              bws.data_ptr(), bws.numel(), arena.data_ptr(), arena.numel(),
+                                              on_ready if on_ready is not None else MOBILENET_READY_FN(), None, _raw_stream(_cur_device()))
+        if rc != 0:
+            self._raise("ttk_mobilenet_backward", rc)
 
     def pwconv_prepared_bytes(self, cin: int, cout: int) -> int:
         return self.cdll.ttk_pwconv_prepared_bytes(cin, cout)
@@ -473,4 +558,5 @@ def exported_symbols() -> list[str]:
             "ttk_pwconv1x1_bwd_fused_rows", "ttk_pwconv1x1_bwd_fused_partial_bytes", "ttk_bc_prepared_bytes", "ttk_bc_partial_rows_pw",
             "ttk_bc_partial_rows_dw", "ttk_bc_partial_rows_pool", "ttk_bc_pw_wgrad_scratch_bytes", "ttk_bc_pw_bwd_fused_rows",
             "ttk_bc_pw_bwd_fused_scratch_bytes", "ttk_bc_pw_wgrad_slices", "ttk_anyc_partial_rows", "ttk_anyc_stem_wgrad_scratch_bytes",
-            "ttk_anyc_dw_wgrad_scratch_bytes", "ttk_anyc_pw_wgrad_scratch_bytes"] + list(_SIGNATURES)
+            "ttk_anyc_dw_wgrad_scratch_bytes", "ttk_anyc_pw_wgrad_scratch_bytes", "ttk_mobilenet_plan_init", "ttk_mobilenet_plan_bytes", "ttk_mobilenet_forward_workspace_bytes",
+            "ttk_mobilenet_backward_workspace_bytes", "ttk_mobilenet_forward", "ttk_mobilenet_backward", "ttk_mobilenet_describe"] + list(_SIGNATURES)

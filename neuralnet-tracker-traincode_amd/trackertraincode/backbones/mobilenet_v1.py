@@ -146,6 +146,49 @@ def get_activation_dtype():
     return t, t
 
 
+# Who issues the launches of a forward / backward pass, an attribute of every MobileNet INSTANCE like the precision (`MobileNet.sequence`,
+# `MobileNet.set_sequence`; not part of `get_config()` / the state dict):
+#   "python"  _forward_impl / _backward_impl below (and _mobilenet_bc.py): one ctypes call and one torch allocation per launch - the default;
+#   "native"  ONE C call per direction (ttk_mobilenet_forward / ttk_mobilenet_backward, csrc/mobilenet_seq.hip), which issues the same entry points
+#             in the same order with the same arguments from one workspace allocation: the host enqueue of the eager step (data-parallel runs,
+#             which cannot replay a graph) without the per-launch Python.  Results are those of "python" (tests/test_native_sequence_gpu.py:
+#             launch lists equal, forward bitwise, gradients bitwise wherever "python" repeats itself bitwise).
+_SEQUENCES = ("python", "native")
+_DEFAULT_SEQUENCE = "python"
+
+
+def _check_sequence(mode):
+    if mode not in _SEQUENCES:
+        raise ValueError(f'sequence must be "python" or "native", got {mode!r}')
+    return mode
+
+
+def set_sequence(mode):
+    """Default launch sequence of MobileNet instances that have not been given one of their own (`MobileNet.set_sequence`): "python" or
+    "native".  Kept for the scripts' `--sequence` flag."""
+    global _DEFAULT_SEQUENCE
+    mode = _check_sequence(mode)
+    if mode == "native":
+        _check_native_product()
+    _DEFAULT_SEQUENCE = mode
+
+
+def get_sequence() -> str:
+    return _DEFAULT_SEQUENCE
+
+
+def _check_native_product():
+    """The native sequence is the PRODUCT configuration of the launch sequences and nothing else: with an experiment switch off its product value
+    it refuses instead of silently running something other than what was asked for."""
+    want = (("_ELIDE_HEAD_INPUT", _THIS, ("dw3_1", "dw4_1")), ("_DW_WGRAD_ROWS", _THIS, 2), ("_FUSED_PW_BWD", _THIS, True), ("_USE_WGRAD_STREAM", _THIS, False),
+            ("_EXP_TENSOR_HOOK", _THIS, None), ("_FOLD_WITH_FINALIZE", _mobilenet_bc, 2), ("BN_PIVOT", _hip, True))
+    for name, mod, value in want:
+        have = getattr(mod, name)
+        if type(have) is not type(value) or have != value:
+            raise ValueError(f'sequence "native" issues the product launch sequence only: {mod.__name__.rsplit(".", 1)[-1]}.{name} is {have!r}, the product '
+                             f'value is {value!r}; use sequence "python" for this experiment')
+
+
 _BN_ROWS = 8  # TTK_BN_ROWS: scale, beta, mean, rstd, ga, gb, gmean, (pad) - see include/ttk.h
 
 
@@ -602,12 +645,76 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
     return grads
 
 
+class _NativeCtx:
+    """What a native forward pass leaves behind for its backward: the plan, ONE workspace and the inputs the backward reads again."""
+    __slots__ = ("plan", "ws", "x", "blur", "blur_arr")
+
+
+def _ptr_array(ts):
+    return (_hip.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _native_forward(x, params, buffers, momentum, eps, mode, blur, precision, blocks):
+    """ttk_mobilenet_forward: the launches of _forward_impl / _mobilenet_bc.forward_impl as one C call.  `mode`: "train" | "frozen" | "eval"."""
+    _check_native_product()
+    L = _hip.lib()
+    blur = list(blur) if blur is not None else [None] * len(blocks)
+    _hip.check_tensors([x], "input")
+    _hip.check_tensors(params, "parameter")
+    _hip.check_tensors(buffers, "BatchNorm buffer")
+    _hip.check_tensors(blur, "blur kernel")
+    B, _, H, W = x.shape
+    plan = L.mobilenet_plan(B, H, W, params[0].shape[0], tuple((cin, cout, stride) for _, cin, cout, stride in blocks), tuple(b is not None for b in blur),
+                            mode, precision, _DETERMINISTIC)
+    c = _NativeCtx()
+    c.plan, c.x, c.blur = plan, x, blur  # (blur: the tensors behind blur_arr stay alive)
+    c.blur_arr = _ptr_array(blur) if any(b is not None for b in blur) else None
+    c.ws = torch.empty(plan.ws_bytes[0], dtype=torch.uint8, device=x.device)
+    feat = torch.empty((B, blocks[-1][2]), dtype=torch.float32, device=x.device)
+    L.mobilenet_forward(plan, x, _ptr_array(params), _ptr_array(buffers), c.blur_arr, float(momentum), float(eps), c.ws, feat)
+    return feat, c
+
+
+def _native_backward(c: _NativeCtx, gfeat, params):
+    """ttk_mobilenet_backward; the gradient arena and `grad_ready_hook` as in _backward_impl (the C side announces parameter ranges through a callback)."""
+    L = _hip.lib()
+    _hip.check_tensors([gfeat], "gradient")
+    _hip.check_tensors(params, "parameter")
+    plan = c.plan
+    offs, total = [], 0
+    for q in params:
+        offs.append(total)
+        total += (q.numel() + 63) // 64 * 64
+    offs.append(total)
+    if total != plan.arena_floats or len(params) != plan.nparams:
+        raise RuntimeError(f"native backward: the parameters take {total} arena floats in {len(params)} tensors, the plan {plan.arena_floats} in {plan.nparams}")
+    arena = torch.empty(total, dtype=torch.float32, device=gfeat.device)  # (zeroed by the C side on this stream)
+    grads = [arena[o:o + q.numel()].view(q.shape) for o, q in zip(offs, params)]
+    bws = torch.empty(plan.ws_bytes[1], dtype=torch.uint8, device=gfeat.device)
+    cb, failed = None, []
+    hook = grad_ready_hook
+    if hook is not None:
+        def ready(_user, first, last):  # (an exception must not unwind through the C frames: kept, raised after the call)
+            if not failed:
+                try:
+                    hook(arena, [(params[i], offs[i], offs[i + 1]) for i in range(first, last)])
+                except BaseException as e:  # noqa: BLE001
+                    failed.append(e)
+        cb = _hip.MOBILENET_READY_FN(ready)
+    L.mobilenet_backward(plan, gfeat, c.x, _ptr_array(params), c.blur_arr, c.ws, bws, arena, cb)
+    if failed:
+        raise failed[0]
+    return grads
+
+
 class _MobileNetFn(torch.autograd.Function):
     """One autograd node for the whole backbone: saves raw conv outputs + BN constants."""
 
     @staticmethod
-    def forward(ctx, x, momentum, eps, buffers, frozen, blur, precision, blocks, *params):
-        if precision == "bf16-compute":
+    def forward(ctx, x, momentum, eps, buffers, frozen, blur, precision, blocks, sequence, *params):
+        if sequence == "native":
+            feat, c = _native_forward(x, params, buffers, momentum, eps, "frozen" if frozen else "train", blur, precision, blocks)
+        elif precision == "bf16-compute":
             feat, c = _mobilenet_bc.forward_impl(_THIS, x, params, buffers, momentum, eps, training=not frozen, frozen=frozen, blur=blur)
         else:
             feat, c = _forward_impl(x, params, buffers, momentum, eps, training=not frozen, frozen=frozen, blur=blur, blocks=blocks)
@@ -619,12 +726,14 @@ class _MobileNetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gfeat):
         params = ctx.saved_tensors
-        if ctx.c.bf == "bc":
+        if isinstance(ctx.c, _NativeCtx):
+            grads = _native_backward(ctx.c, gfeat.contiguous(), params)
+        elif ctx.c.bf == "bc":
             grads = _mobilenet_bc.backward_impl(_THIS, ctx.c, gfeat.contiguous(), params)
         else:
             grads = _backward_impl(ctx.c, gfeat.contiguous(), params)
         ctx.c = None
-        return (None, None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, None, *grads)
 
 
 class MobileNet(nn.Module):
@@ -644,6 +753,7 @@ class MobileNet(nn.Module):
             return DepthWiseBlock(inplanes, planes, stride=stride, momentum=momentum, use_blurpool=use_blurpool)
 
         self.use_blurpool = bool(use_blurpool)
+        self.sequence = None   # None = the module-wide default (set_sequence); "python" | "native" through MobileNet.set_sequence
         self.precision = None  # None = the module-wide default (set_activation_dtype); "fp32" | "bf16-compute" through set_precision
         self.conv1 = nn.Conv2d(input_channel, c0, kernel_size=5, stride=2, padding=2, bias=False)
         self.bn1 = NormalizationLayer(c0, momentum=momentum)
@@ -669,6 +779,18 @@ class MobileNet(nn.Module):
         self._check_width_precision(mode)
         self.precision = mode
         return self
+
+    # ---- who issues the launches (an attribute of the instance; not in the checkpoint) ---------------------------
+    def set_sequence(self, mode):
+        """"python" | "native" for THIS backbone (None: follow the module-wide default again).  Returns self."""
+        mode = None if mode is None else _check_sequence(mode)
+        if mode == "native":
+            _check_native_product()
+        self.sequence = mode
+        return self
+
+    def effective_sequence(self) -> str:
+        return self.sequence if getattr(self, "sequence", None) is not None else _DEFAULT_SEQUENCE
 
     def effective_precision(self) -> str:
         return self.precision if getattr(self, "precision", None) is not None else _DEFAULT_PRECISION
@@ -735,7 +857,7 @@ class MobileNet(nn.Module):
         x = x.contiguous()
         bn_training = [bn.training for bn in self._bns()]
         if self.training and all(bn_training):
-            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), False, self._blur_weights(), self.effective_precision(), self._blocks, *self._flat_params())
+            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), False, self._blur_weights(), self.effective_precision(), self._blocks, self.effective_sequence(), *self._flat_params())
         if any(bn_training):
             raise NotImplementedError("mixed train/eval BatchNorm layers are not supported by the fused backbone")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params()):
@@ -744,8 +866,11 @@ class MobileNet(nn.Module):
             if any(p.requires_grad for bn in self._bns() for p in bn.parameters()):
                 raise NotImplementedError("eval-mode BatchNorm layers with trainable weight / bias are not built: freeze them "
                                           "(modelcomponents.freeze_norm_stats) or put the layers in training mode")
-            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), True, self._blur_weights(), self.effective_precision(), self._blocks, *self._flat_params())
-        if self.effective_precision() == "bf16-compute":
+            return _MobileNetFn.apply(x, momentum, eps, self._flat_buffers(), True, self._blur_weights(), self.effective_precision(), self._blocks, self.effective_sequence(), *self._flat_params())
+        if self.effective_sequence() == "native":
+            feat, _ = _native_forward(x, [q.detach() for q in self._flat_params()], self._flat_buffers(), momentum, eps, "eval", self._blur_weights(),
+                                      self.effective_precision(), self._blocks)
+        elif self.effective_precision() == "bf16-compute":
             feat, _ = _mobilenet_bc.forward_impl(_THIS, x, [q.detach() for q in self._flat_params()], self._flat_buffers(), momentum, eps, False,
                                                  blur=self._blur_weights())
         else:
