@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 34
+#define TTK_ABI_VERSION 35
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -752,6 +752,26 @@ int ttk_clip_adam(const int64_t* ptrs, const int32_t* numel, const int32_t* grou
                   const float* lr4, const float* wd4, float beta1, float beta2, float eps, float max_norm,
                   float grad_scale, float* steps, float* partial, float* out_norm, const float* hyper_dev,
                   ttk_stream_t stream);
+/* (ABI 35) ttk_clip_adam_guarded: ttk_clip_adam with a non-finite guard decided on the device.  Same arguments plus `health` (DEVICE
+ * int32[TTK_ADAM_HEALTH_WORDS], zero-initialised by the caller with -1 in the culprit word).  The step is BAD when the fixed-order fp64 sum
+ * of the chunk partials, or the total norm derived from it, is not finite - every workgroup forms that sum identically, so the verdict is
+ * uniform without an extra pass or atomics.  A finite gradient whose squared norm overflows fp32 (|g| > 1.8e19) counts as bad.
+ *   bad step:  parameters, exp_avg, exp_avg_sq and steps[] end the call bitwise as they began (the increment of steps[] is taken back by
+ *              the workgroup that owns the tensor's first chunk: exact below 2^24); out_norm receives the non-finite total;
+ *              health[SKIPPED] += 1, health[CONSECUTIVE] += 1, health[CULPRIT] = tensor index of the lowest-numbered chunk whose partial
+ *              is not finite.
+ *   good step: bitwise what ttk_clip_adam produces from the same state; health[CONSECUTIVE] = 0.
+ * Workgroup 0 writes `health` with plain stores.  Nothing about the verdict is a launch argument or a host read: the call captures and
+ * replays in a hipGraph like ttk_clip_adam.  ttk_clip_adam itself runs the unguarded instantiation of the kernels, unchanged. */
+#define TTK_ADAM_HEALTH_SKIPPED 0     /* bad steps so far */
+#define TTK_ADAM_HEALTH_CONSECUTIVE 1 /* bad steps since the last good one */
+#define TTK_ADAM_HEALTH_CULPRIT 2     /* tensor index blamed for the most recent bad step; -1 before any */
+#define TTK_ADAM_HEALTH_WORDS 4
+int ttk_clip_adam_guarded(const int64_t* ptrs, const int32_t* numel, const int32_t* group,
+                          const int32_t* chunk_tensor, const int32_t* chunk_offset, int nchunks, int chunk_size,
+                          const float* lr4, const float* wd4, float beta1, float beta2, float eps, float max_norm,
+                          float grad_scale, float* steps, float* partial, float* out_norm, const float* hyper_dev,
+                          int32_t* health, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-GPU affine-warp augmentation (the reference does this per sample on the CPU with OpenCV inside

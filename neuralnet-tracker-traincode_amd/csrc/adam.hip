@@ -7,6 +7,9 @@
 //   pass 1: partial[c] = sum g^2 over the chunk
 //   pass 2: every block re-adds the partials in a fixed order (fp64) -> total norm -> clip coefficient
 //           -> Adam update of its chunk.  Deterministic.
+// ttk_clip_adam_guarded runs clip_adam_k<true>: the same pass 2 that first judges the sum it has just formed and, when that is not finite,
+// leaves parameters, moments and step counts as they were (include/ttk.h).  ttk_clip_adam runs clip_adam_k<false>, in which no line of
+// the guard is compiled.  Pass 1 is shared: nothing in it depends on the verdict.
 #include "ttk_common.h"
 
 namespace ttk {
@@ -62,9 +65,16 @@ __global__ void __launch_bounds__(kBlock) grad_sqnorm_k(AdamTables t, int chunk_
   if (threadIdx.x == 0) partial[c] = acc;
 }
 
+// (bit tests: they mean the same under any floating-point flags of the build)
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ bool not_finite(double x) {
+  return ((unsigned long long)__double_as_longlong(x) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+}
+
+template <bool GUARD>
 __global__ void __launch_bounds__(kBlock) clip_adam_k(AdamTables t, AdamHyper h, int chunk_size, int nchunks,
                                                        const float* __restrict__ partial, float* __restrict__ out_norm,
-                                                       const float* __restrict__ hyper_dev) {
+                                                       const float* __restrict__ hyper_dev, int32_t* __restrict__ health) {
   __shared__ double dred[kBlock];
   // total gradient norm: fixed-order fp64 sum of the chunk partials (identical in every block)
   double acc = 0.0;
@@ -78,6 +88,40 @@ __global__ void __launch_bounds__(kBlock) clip_adam_k(AdamTables t, AdamHyper h,
   // grad_scale: the gradients in memory are SUMS over data-parallel replicas; every use below sees grad_scale * g
   const float total = h.grad_scale * (float)sqrt(dred[0]);
   if (blockIdx.x == 0 && threadIdx.x == 0 && out_norm) *out_norm = total;
+  if constexpr (GUARD) {
+    // the verdict: dred[0] is the same number in every workgroup, so all of them take the same side without talking to one another
+    const bool bad = not_finite(dred[0]) || not_finite(total);
+    if (blockIdx.x == 0) {
+      if (bad) {
+        // culprit: the tensor of the lowest-numbered chunk whose partial is not finite (workgroup 0 only, bad steps only)
+        __shared__ int first[kBlock];
+        int lo = 0x7fffffff;
+        for (int i = threadIdx.x; i < nchunks; i += kBlock)
+          if (not_finite(partial[i])) { lo = i; break; }  // (i ascends: the thread's first hit is its lowest)
+        first[threadIdx.x] = lo;
+        __syncthreads();
+        for (int s = kBlock / 2; s > 0; s >>= 1) {
+          if (threadIdx.x < s) first[threadIdx.x] = min(first[threadIdx.x], first[threadIdx.x + s]);
+          __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+          health[TTK_ADAM_HEALTH_SKIPPED] += 1;
+          health[TTK_ADAM_HEALTH_CONSECUTIVE] += 1;
+          health[TTK_ADAM_HEALTH_CULPRIT] = first[0] < nchunks ? t.chunk_tensor[first[0]] : -1;
+        }
+      } else if (threadIdx.x == 0) {
+        health[TTK_ADAM_HEALTH_CONSECUTIVE] = 0;
+      }
+    }
+    if (bad) {
+      // pass 1 has counted this step for every tensor with a gradient; no workgroup reads steps[] on this side, so the owner of the
+      // tensor's first chunk takes the increment back ((n + 1) - 1 == n exactly for counts below 2^24)
+      const int c = blockIdx.x;
+      const int ti = t.chunk_tensor[c];
+      if (t.chunk_offset[c] == 0 && t.ptrs[4 * ti + 1] != 0 && threadIdx.x == 0) t.steps[ti] -= 1.f;
+      return;
+    }
+  }
   float coef = h.grad_scale;
   if (h.max_norm > 0.f) coef *= fminf(h.max_norm / (total + 1.0e-6f), 1.f);  // torch.nn.utils.clip_grad_norm_
 
@@ -127,6 +171,25 @@ __global__ void __launch_bounds__(kBlock) clip_adam_k(AdamTables t, AdamHyper h,
   }
 }
 
+template <bool GUARD>
+static int clip_adam_launch(const char* name, const int64_t* ptrs, const int32_t* numel, const int32_t* group, const int32_t* chunk_tensor,
+                            const int32_t* chunk_offset, int nchunks, int chunk_size, const float* lr4, const float* wd4, float beta1,
+                            float beta2, float eps, float max_norm, float grad_scale, float* steps, float* partial, float* out_norm,
+                            const float* hyper_dev, int32_t* health, ttk_stream_t stream) {
+  TTK_REQUIRE(ptrs && numel && group && chunk_tensor && chunk_offset && lr4 && wd4 && partial && steps, "%s: null pointer", name);
+  TTK_REQUIRE(!GUARD || health, "%s: null health block (device int32[TTK_ADAM_HEALTH_WORDS])", name);
+  TTK_REQUIRE(nchunks > 0 && chunk_size > 0, "%s: bad chunking", name);
+  TTK_REQUIRE(grad_scale > 0.f, "%s: grad_scale must be positive (1 / number of replicas)", name);
+  AdamTables t{ptrs, numel, group, chunk_tensor, chunk_offset, steps};
+  AdamHyper h;
+  for (int i = 0; i < TTK_ADAM_MAX_GROUPS; ++i) { h.lr[i] = lr4[i]; h.wd[i] = wd4[i]; }
+  h.beta1 = beta1; h.beta2 = beta2; h.eps = eps; h.max_norm = max_norm; h.grad_scale = grad_scale;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_sqnorm_k, dim3(nchunks), dim3(kBlock), 0, st, t, chunk_size, partial);
+  hipLaunchKernelGGL(clip_adam_k<GUARD>, dim3(nchunks), dim3(kBlock), 0, st, t, h, chunk_size, nchunks, partial, out_norm, hyper_dev, health);
+  TTK_LAUNCH_CHECK(name);
+}
+
 }  // namespace ttk
 
 using namespace ttk;
@@ -137,17 +200,16 @@ int ttk_clip_adam(const int64_t* ptrs, const int32_t* numel, const int32_t* grou
                   const int32_t* chunk_offset, int nchunks, int chunk_size, const float* lr4, const float* wd4, float beta1,
                   float beta2, float eps, float max_norm, float grad_scale, float* steps, float* partial,
                   float* out_norm, const float* hyper_dev, ttk_stream_t stream) {
-  TTK_REQUIRE(ptrs && numel && group && chunk_tensor && chunk_offset && lr4 && wd4 && partial && steps, "clip_adam: null pointer");
-  TTK_REQUIRE(nchunks > 0 && chunk_size > 0, "clip_adam: bad chunking");
-  TTK_REQUIRE(grad_scale > 0.f, "clip_adam: grad_scale must be positive (1 / number of replicas)");
-  AdamTables t{ptrs, numel, group, chunk_tensor, chunk_offset, steps};
-  AdamHyper h;
-  for (int i = 0; i < TTK_ADAM_MAX_GROUPS; ++i) { h.lr[i] = lr4[i]; h.wd[i] = wd4[i]; }
-  h.beta1 = beta1; h.beta2 = beta2; h.eps = eps; h.max_norm = max_norm; h.grad_scale = grad_scale;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(grad_sqnorm_k, dim3(nchunks), dim3(kBlock), 0, st, t, chunk_size, partial);
-  hipLaunchKernelGGL(clip_adam_k, dim3(nchunks), dim3(kBlock), 0, st, t, h, chunk_size, nchunks, partial, out_norm, hyper_dev);
-  TTK_LAUNCH_CHECK("clip_adam");
+  return clip_adam_launch<false>("clip_adam", ptrs, numel, group, chunk_tensor, chunk_offset, nchunks, chunk_size, lr4, wd4, beta1, beta2, eps,
+                                 max_norm, grad_scale, steps, partial, out_norm, hyper_dev, nullptr, stream);
+}
+
+int ttk_clip_adam_guarded(const int64_t* ptrs, const int32_t* numel, const int32_t* group, const int32_t* chunk_tensor,
+                          const int32_t* chunk_offset, int nchunks, int chunk_size, const float* lr4, const float* wd4, float beta1,
+                          float beta2, float eps, float max_norm, float grad_scale, float* steps, float* partial,
+                          float* out_norm, const float* hyper_dev, int32_t* health, ttk_stream_t stream) {
+  return clip_adam_launch<true>("clip_adam_guarded", ptrs, numel, group, chunk_tensor, chunk_offset, nchunks, chunk_size, lr4, wd4, beta1, beta2,
+                                eps, max_norm, grad_scale, steps, partial, out_norm, hyper_dev, health, stream);
 }
 
 }  // extern "C"

@@ -60,7 +60,7 @@ def setup_lr_with_slower_variance_training(net, base_lr):
 def create_optimizer(net, args):
     """Fused clip(1.0)+Adam over the reference's three parameter groups and its LR schedule."""
     groups = [g for g in setup_lr_with_slower_variance_training(net, args.lr) if g["params"]]
-    optimizer = train.ClipAdam(groups, lr=args.lr, max_norm=1.0)
+    optimizer = train.ClipAdam(groups, lr=args.lr, max_norm=1.0, skip_nonfinite=bool(getattr(args, "skip_nonfinite", False)))
     n_epochs = args.epochs
     scheduler = train.ExponentialUpThenSteps(optimizer, max(1, n_epochs // 10), 0.1, [n_epochs // 2])
     return optimizer, scheduler
@@ -193,7 +193,40 @@ def make_parser():
                    help="with --graph-steps: per-tag (one graph per sub-batch layout) | flat (the step runs over all B rows with a Tag code per row and "
                    "a device table of loss weights: ONE graph for any per-Tag split and through a weight ramp; train.flat_training_step).  "
                    "Data-parallel runs stay eager either way")
+    # long runs on a shared pool (no counterpart in the reference's flags; Lightning's ModelCheckpoint(save_weights_only=False) is)
+    p.add_argument("--save-state-every", default=0, type=int, dest="save_state_every", metavar="N",
+                   help="write the run state (weights, optimiser, scheduler, SWA average, best validation value, every random stream of the data "
+                   "path) to <outdir>/<net>/train_state.pt after every N epochs; 0 (default): never")
+    p.add_argument("--resume", default=None, type=str, metavar="PATH|auto",
+                   help="continue from a run state: a file, or auto = the output directory's train_state.pt if present, else a fresh start.  The "
+                   "arguments that shape model, data and schedule must be those of the run that wrote it")
+    p.add_argument("--stop-after-epoch", default=None, type=int, dest="stop_after_epoch", metavar="N",
+                   help="leave once N epochs are complete: save the run state and exit 0 (time-sliced jobs; continue with --resume)")
+    p.add_argument("--skip-nonfinite", default=False, action="store_true", dest="skip_nonfinite",
+                   help="optimiser steps whose gradient norm is not finite are skipped on the device (train.ClipAdam(skip_nonfinite=True)); ten in a "
+                   "row end the run with NonFiniteGradientError")
     return p
+
+
+# arguments a resumed run may change: where and how the run is driven, not what it computes
+RESUME_FREE_ARGS = ("outdir", "sequence", "graph_steps", "graph_layout", "stop_after_epoch", "save_state_every", "resume")
+
+
+def recorded_args(args) -> dict:
+    """The arguments a run state records: the parser's namespace minus RESUME_FREE_ARGS."""
+    known = vars(make_parser().parse_args([]))
+    return {k: getattr(args, k) for k in known if k not in RESUME_FREE_ARGS and hasattr(args, k)}
+
+
+def check_resume_args(saved: dict, current: dict):
+    """ValueError naming the flag when a recorded argument differs between the run that wrote the state and this one."""
+    flags = {a.dest: (a.option_strings[0] if a.option_strings else a.dest) for a in make_parser()._actions}
+    for k in sorted(set(saved) | set(current)):
+        if k in RESUME_FREE_ARGS:
+            continue
+        if k not in saved or k not in current or saved[k] != current[k]:
+            raise ValueError(f"--resume: {flags.get(k, k)} is {current.get(k, '<absent>')!r} here, the run state was written with "
+                             f"{saved.get(k, '<absent>')!r}; a run continues with the arguments it was started with")
 
 
 def graph_mode(args):
@@ -236,6 +269,20 @@ def main():
     callbacks = [train.CheckpointCallback(out_dir)] if rank == 0 else []
     if args.swa and rank == 0:
         callbacks.append(train.SwaCallback(start_epoch=args.epochs * 2 // 3))
+    run_state = None
+    if args.save_state_every or args.stop_after_epoch is not None or args.resume:
+        state_path = join(out_dir, "train_state.pt")
+        resume = None
+        if args.resume:
+            path = state_path if args.resume == "auto" else args.resume
+            if os.path.exists(path):
+                resume = train.load_run_state(path, rank=rank, world=world)
+                check_resume_args(resume["meta"].get("args", {}), recorded_args(args))
+            elif args.resume != "auto":
+                raise FileNotFoundError(f"--resume {path}: no such run state")
+        run_state = train.RunState(state_path, every=args.save_state_every, stop_after_epoch=args.stop_after_epoch, resume=resume,
+                                   meta={"args": recorded_args(args)}, rank=rank, world=world)
+    stopped_early = args.stop_after_epoch is not None and args.stop_after_epoch < args.epochs
     reducer = None
     if world > 1:
         reducer = parallel.GradAllReduce()
@@ -245,7 +292,7 @@ def main():
     try:
         train.fit(net, train_loader, train_crit, optimizer, scheduler, epochs=args.epochs, callbacks=callbacks,
                   val_loader=test_loader if rank == 0 else None, val_criterions=test_crit, reducer=reducer,
-                  graphed=graph_mode(args) if reducer is None else False)
+                  graphed=graph_mode(args) if reducer is None else False, run_state=run_state)
     finally:
         parallel.install(None)
     if rank == 0:
@@ -253,7 +300,7 @@ def main():
         if not os.path.exists(join(out_dir, "last.ckpt")):  # (no validation epoch ran)
             models.save_model(net.to("cpu"), join(out_dir, "last.ckpt"))
         for cb in callbacks:
-            if hasattr(cb, "on_train_end"):
+            if hasattr(cb, "on_train_end") and not stopped_early:  # (swa.ckpt is the finished run's average)
                 cb.on_train_end(out_dir)
     if world > 1:
         dist.barrier()

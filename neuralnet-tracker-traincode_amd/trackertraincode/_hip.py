@@ -104,6 +104,7 @@ _SIGNATURES = {
     "ttk_affine_labels2d": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "ttk_intensity_augment": [_P, _P, _P, _P, _I, _I, _I, _F],
     "ttk_clip_adam": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P],
+    "ttk_clip_adam_guarded": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P],
     "ttk_stream_probe": [_P, _P, _P, _L, _I, _I, _I, _I, _L, _I, _I, _I],
     # bf16-compute path (csrc/bc_*.hip)
     "ttk_bc_prepare_weights": [_I, _P, _P, _P, _P],
@@ -129,7 +130,9 @@ _SIGNATURES = {
     "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 34
+ABI_VERSION = 35
+
+ADAM_HEALTH_SKIPPED, ADAM_HEALTH_CONSECUTIVE, ADAM_HEALTH_CULPRIT, ADAM_HEALTH_WORDS = 0, 1, 2, 4  # TTK_ADAM_HEALTH_*
 
 
 # Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the

@@ -144,6 +144,37 @@ class ResidentLoader:
     def __len__(self):
         return self.steps
 
+    @staticmethod
+    def _rng_state(rng: np.random.RandomState) -> dict:
+        name, keys, pos, has_gauss, cached = rng.get_state()  # as tensors and plain numbers: the state loads with torch.load(weights_only=True)
+        return {"name": str(name), "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos), "has_gauss": int(has_gauss), "cached": float(cached)}
+
+    @staticmethod
+    def _set_rng_state(rng: np.random.RandomState, st: dict):
+        rng.set_state((st["name"], st["keys"].numpy().astype(np.uint32), st["pos"], st["has_gauss"], st["cached"]))
+
+    def state_dict(self) -> dict:
+        """The loader's random streams between two epochs (the prefetch thread of host-placed frames has finished its `steps` draws by
+        then): the dataset choice, the permutations with their read positions and the generator they are renewed from, the torch generator
+        of the crop and the intensity parameters, and the generators of intensity containers that bring their own."""
+        return {"choose": self._rng_state(self._choose.rng), "rng": self._rng_state(self._rng),
+                "perm": [torch.from_numpy(np.asarray(p, dtype=np.int64)) for p in self._perm], "pos": [int(v) for v in self._pos],
+                "gen": self._gen.get_state(), "augs": [a.generator.get_state() if a.generator is not None else None for a in self._augs]}
+
+    def load_state_dict(self, state: dict):
+        if [len(p) for p in state["perm"]] != [len(d) for d in self.datasets] or len(state["augs"]) != len(self._augs):
+            raise ValueError("ResidentLoader.load_state_dict: the state is of a loader over other datasets or augmentations")
+        self._set_rng_state(self._choose.rng, state["choose"])
+        self._set_rng_state(self._rng, state["rng"])
+        self._perm = [p.numpy().copy() for p in state["perm"]]
+        self._pos = [int(v) for v in state["pos"]]
+        self._gen.set_state(state["gen"])
+        for a, st in zip(self._augs, state["augs"]):
+            if (st is None) != (a.generator is None):
+                raise ValueError("ResidentLoader.load_state_dict: an intensity container has a generator on one side only")
+            if st is not None:
+                a.generator.set_state(st)
+
     def _next_indices(self, d: int, n: int) -> np.ndarray:
         out = []
         while n > 0:

@@ -136,6 +136,26 @@ class SyntheticPoseLoader:
     def __len__(self):
         return self._steps
 
+    def state_dict(self) -> dict:
+        """Every random stream the loader draws from, as it stands between two epochs: the samples' generator, the split generator of
+        `vary_split`, and the generators of the intensity containers (the Gaussian noise itself comes from the device's default CUDA
+        generator, which belongs to the run state, not to the loader)."""
+        return {"gen": self._gen.get_state(), "split_gen": self._split_gen.get_state() if self._vary else None,
+                "augs": [a.generator.get_state() if a.generator is not None else None for a in (self._augs or [])]}
+
+    def load_state_dict(self, state: dict):
+        augs = self._augs or []
+        if (state["split_gen"] is not None) != self._vary or len(state["augs"]) != len(augs):
+            raise ValueError("SyntheticPoseLoader.load_state_dict: the state is of a loader built differently (vary_split / image augmentations)")
+        self._gen.set_state(state["gen"])
+        if self._vary:
+            self._split_gen.set_state(state["split_gen"])
+        for a, st in zip(augs, state["augs"]):
+            if (st is None) != (a.generator is None):
+                raise ValueError("SyntheticPoseLoader.load_state_dict: an intensity container has a generator on one side only")
+            if st is not None:
+                a.generator.set_state(st)
+
     def __iter__(self) -> Iterator[list[Batch]]:
         for _ in range(self._steps):
             plan = self._plan

@@ -271,12 +271,20 @@ class ClipAdam(torch.optim.Optimizer):
     State layout matches torch.optim.Adam (`step`, `exp_avg`, `exp_avg_sq`); the step counts live on the device (the
     kernel advances them), so a step can be captured in a hipGraph and `state_dict()` / `load_state_dict()` resume
     exactly.  `grad_scale` (default 1): the stored gradients are read as grad_scale * g - 1/world when a
-    data-parallel all-reduce left sums in place (trackertraincode.parallel)."""
+    data-parallel all-reduce left sums in place (trackertraincode.parallel).
+
+    `skip_nonfinite=True`: the step runs `ttk_clip_adam_guarded`.  A step whose total gradient norm is not finite (a NaN or Inf anywhere
+    in the gradients, or a finite gradient whose squared norm overflows float32) changes neither parameters nor moments nor step counts;
+    the kernel decides this on the device, so the step still has no host synchronisation and still captures in a hipGraph.  `health()`
+    reads the device counters (one device read: call it per epoch, never per step).  The guard protects the weights and the optimiser
+    state only: BatchNorm running statistics that a non-finite forward has already written stay written, and the backbone kernels treat
+    non-finite inputs as before.  A good step is bitwise the unguarded step."""
 
     MAX_GROUPS = 128  # TTK_ADAM_MAX_GROUPS (prepare_finetune() of the default backbone returns 66, one per backbone sub-module)
     CHUNK = 4096  # elements per workgroup: ~800 workgroups for the 3.2 M parameters (16384 left most of the 256 CUs idle)
 
-    def __init__(self, params, lr=1.0e-3, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0, max_norm: float | None = 1.0):
+    def __init__(self, params, lr=1.0e-3, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0, max_norm: float | None = 1.0,
+                 skip_nonfinite: bool = False):
         # capturable: torch then keeps a loaded `step` as a float32 tensor on the parameter's device
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=True))
         self.param_groups = [g for g in self.param_groups]
@@ -286,6 +294,8 @@ class ClipAdam(torch.optim.Optimizer):
             raise ValueError("all groups must share betas and eps")
         self.max_norm = max_norm
         self.grad_scale = 1.0
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._health_host = [0, 0, -1]  # (skipped, consecutive, culprit) the device block starts from when the tables are (re)built
         self._tables = None
         self._uploaded = None      # gradient addresses the device table currently holds
         self._upload_event = None  # recorded behind the last upload of the pinned table
@@ -293,7 +303,30 @@ class ClipAdam(torch.optim.Optimizer):
         self.last_grad_norm: Tensor | None = None
 
     def _invalidate(self):
+        T = getattr(self, "_tables", None)
+        if T is not None and T.get("health") is not None:  # the counters outlive the device tables (one device read: rare)
+            self._health_host = T["health"][:3].tolist()
         self._tables, self._uploaded, self._upload_event = None, None, None
+
+    def health(self) -> dict:
+        """{"skipped", "consecutive", "culprit_index"} of a `skip_nonfinite` optimiser: bad steps so far, bad steps since the last good one,
+        and the index (in the order of the parameter groups' parameters) of the first tensor with a non-finite gradient in the most recent
+        bad step, -1 before any.  One device read, which waits for the steps enqueued so far."""
+        if not self.skip_nonfinite:
+            raise RuntimeError("ClipAdam.health(): the optimiser was built without skip_nonfinite=True")
+        T = self._tables
+        h = T["health"][:3].tolist() if T is not None else list(self._health_host)
+        return {"skipped": int(h[0]), "consecutive": int(h[1]), "culprit_index": int(h[2])}
+
+    def load_health(self, health: dict):
+        """Restore the counters `health()` returned (resume)."""
+        self._health_host = [int(health["skipped"]), int(health["consecutive"]), int(health["culprit_index"])]
+        if self._tables is not None and self._tables.get("health") is not None:
+            self._tables["health"][:3] = torch.tensor(self._health_host, dtype=torch.int32)
+
+    def parameter_at(self, index: int):
+        """The parameter behind a `culprit_index`."""
+        return [p for g in self.param_groups for p in g["params"]][index]
 
     def load_state_dict(self, state_dict):
         """Resume: the loaded moments / step counts replace the live ones, so every cached device address is stale."""
@@ -340,6 +373,8 @@ class ClipAdam(torch.optim.Optimizer):
             ptrs=torch.zeros((len(plist), 4), dtype=torch.int64, device=dev), steps=steps,
             partial=torch.empty(len(ct), dtype=torch.float32, device=dev), norm=torch.zeros(1, dtype=torch.float32, device=dev),
             hyper=torch.zeros(2 * self.MAX_GROUPS, dtype=torch.float32, device=dev),  # TTK_ADAM_HYPER_* block (include/ttk.h)
+            # TTK_ADAM_HEALTH_* block of the guarded entry point
+            health=torch.tensor(list(self._health_host) + [0] * (_hip.ADAM_HEALTH_WORDS - 3), dtype=torch.int32, device=dev) if self.skip_nonfinite else None,
         )
         h = self._tables["ptrs_host"]
         for ti, p in enumerate(plist):
@@ -386,9 +421,13 @@ class ClipAdam(torch.optim.Optimizer):
         # inside a hipGraph capture nothing of the step may be baked into launch arguments: learning rates and weight
         # decays are read from the device block `hyper` (the step counts always live on the device)
         hyper = p_(T["hyper"]) if capturing else None
-        _hip.lib().call("ttk_clip_adam", p_(T["ptrs"]), p_(T["numel"]), p_(T["group"]), p_(T["chunk_tensor"]), p_(T["chunk_offset"]),
-                        T["nchunks"], self.CHUNK, lr4, wd4, b1, b2, self.param_groups[0]["eps"], float(self.max_norm or 0.0),
-                        float(self.grad_scale), p_(T["steps"]), p_(T["partial"]), p_(T["norm"]), hyper)
+        args = (p_(T["ptrs"]), p_(T["numel"]), p_(T["group"]), p_(T["chunk_tensor"]), p_(T["chunk_offset"]),
+                T["nchunks"], self.CHUNK, lr4, wd4, b1, b2, self.param_groups[0]["eps"], float(self.max_norm or 0.0),
+                float(self.grad_scale), p_(T["steps"]), p_(T["partial"]), p_(T["norm"]), hyper)
+        if self.skip_nonfinite:
+            _hip.lib().call("ttk_clip_adam_guarded", *args, p_(T["health"]))
+        else:
+            _hip.lib().call("ttk_clip_adam", *args)
         if not capturing:
             self._t += 1
         self.last_grad_norm = T["norm"]
@@ -459,6 +498,18 @@ class SwaCallback:
     def on_train_end(self, root_dir: str):
         assert self._swa_model is not None
         save_model(self._swa_model, os.path.join(root_dir, "swa.ckpt"))
+
+    def state_dict(self) -> dict:
+        sd = None if self._swa_model is None else {k: v.detach().clone() for k, v in self._swa_model.state_dict().items()}
+        return {"n_averaged": int(self.n_averaged), "swa_model": sd}
+
+    def load_state_dict(self, state: dict):
+        """After `on_train_start` (which makes the averaged model as a copy of the live one): the average so far replaces that copy."""
+        if state["swa_model"] is not None:
+            if self._swa_model is None:
+                raise RuntimeError("SwaCallback.load_state_dict: call on_train_start(model) first - it creates the averaged model")
+            self._swa_model.load_state_dict(state["swa_model"])
+        self.n_averaged = int(state["n_averaged"])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1003,6 +1054,12 @@ class CheckpointCallback:
         os.makedirs(self.dirpath, exist_ok=True)
         save_model(copy.deepcopy(model).to("cpu"), path)
 
+    def state_dict(self) -> dict:
+        return {"best_value": float(self.best_value), "best_epoch": int(self.best_epoch), "history": [float(v) for v in self.history]}
+
+    def load_state_dict(self, state: dict):
+        self.best_value, self.best_epoch, self.history = float(state["best_value"]), int(state["best_epoch"]), [float(v) for v in state["history"]]
+
     def on_validation_end(self, epoch: int, model: nn.Module, val_loss: float):
         self.history.append(val_loss)
         self._save(model, self.last_model_path)
@@ -1011,8 +1068,179 @@ class CheckpointCallback:
             self._save(model, self.best_model_path)
 
 
+class NonFiniteGradientError(RuntimeError):
+    """`fit()`: a `skip_nonfinite` optimiser has skipped `max_consecutive_skips` steps in a row."""
+
+
+# ---------------------------------------------------------------------------------------------
+# run state: everything a run stopped after an epoch needs to go on as if it had not been stopped
+# ---------------------------------------------------------------------------------------------
+RUN_STATE_VERSION = 1
+
+
+class RunState:
+    """What `fit(run_state=...)` saves and resumes from.
+
+    `path`: the file (one `torch.save`; data-parallel replicas add `<path>.rank<r>`, below).  `every`: save after every that many
+    epochs (0: only when `stop_after_epoch` is reached).  `stop_after_epoch=N`: leave the loop once N epochs are complete, after saving.
+    `resume`: what `load_run_state(path)` returned, or None for a fresh start.  `meta`: plain data stored beside the state (the training
+    script records its arguments there).  `objects`: {name: object with state_dict() / load_state_dict()} captured on top of what fit()
+    captures itself - model, optimiser (+ health counters), scheduler, every callback and loader that has state_dict(), torch's global CPU
+    generator and the device's default CUDA generator.
+    `rank` / `world`: BatchNorm running statistics and the data streams are per replica.  Rank 0 writes `path` (weights, optimiser,
+    scheduler, callbacks); every rank, rank 0 included, writes `<path>.rank<r>` with its loaders, generators and module buffers.  A state
+    written by another `world` is refused."""
+
+    def __init__(self, path: str, every: int = 1, stop_after_epoch: int | None = None, resume: dict | None = None, meta: dict | None = None,
+                 objects: dict | None = None, rank: int = 0, world: int = 1):
+        self.path, self.every, self.stop_after_epoch, self.resume = str(path), int(every), stop_after_epoch, resume
+        self.meta, self.objects, self.rank, self.world = dict(meta or {}), dict(objects or {}), int(rank), int(world)
+
+    def rank_path(self, rank: int | None = None) -> str:
+        return f"{self.path}.rank{self.rank if rank is None else rank}"
+
+    def due(self, next_epoch: int) -> bool:
+        return (self.every > 0 and next_epoch % self.every == 0) or self.stops(next_epoch)
+
+    def stops(self, next_epoch: int) -> bool:
+        return self.stop_after_epoch is not None and next_epoch >= int(self.stop_after_epoch)
+
+
+def _atomic_torch_save(obj, path: str):
+    """torch.save to a temporary name in the same directory, then os.replace: a write that fails leaves the previous file intact."""
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    tmp = os.path.join(d, f".{os.path.basename(path)}.tmp{os.getpid()}")
+    try:
+        with open(tmp, "wb") as f:
+            torch.save(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+
+
+def _cpu(obj):
+    if torch.is_tensor(obj):
+        return obj.detach().to("cpu").clone()
+    if isinstance(obj, dict):
+        return {k: _cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_cpu(v) for v in obj)
+    return obj
+
+
+def _stateful(objs: dict) -> dict:
+    return {k: o for k, o in objs.items() if o is not None and hasattr(o, "state_dict") and hasattr(o, "load_state_dict")}
+
+
+def _rng_state(device) -> dict:
+    out = {"cpu": torch.get_rng_state()}
+    if device is not None and device.type == "cuda":
+        out["cuda"] = torch.cuda.get_rng_state(device)
+    return out
+
+
+def _set_rng_state(state: dict, device):
+    torch.set_rng_state(state["cpu"])
+    if "cuda" in state:
+        if device is None or device.type != "cuda":
+            raise ValueError("the run state holds a CUDA generator state, the model is not on a GPU")
+        torch.cuda.set_rng_state(state["cuda"], device)
+
+
+def _model_device(model):
+    p = next(iter(model.parameters()), None)
+    return None if p is None else p.device
+
+
+def save_run_state(path, model, optimizer=None, scheduler=None, next_epoch=0, callbacks=(), train_loader=None, val_loader=None, objects=None,
+                   meta=None, rank=0, world=1):
+    """Write the run state at an epoch boundary (RunState; `fit(run_state=...)` calls this).  One `torch.save` file per call, written
+    under a temporary name and moved into place.  Tensors are stored on the CPU.  With `world > 1` rank 0 writes `path` and every rank
+    writes `<path>.rank<r>`."""
+    device = _model_device(model)
+    per_rank = {"version": RUN_STATE_VERSION, "next_epoch": int(next_epoch), "world": int(world), "rank": int(rank), "rng": _rng_state(device),
+                "loaders": {k: _cpu(o.state_dict()) for k, o in _stateful({"train": train_loader, "val": val_loader}).items()},
+                "objects": {k: _cpu(o.state_dict()) for k, o in _stateful(dict(objects or {})).items()}}
+    shared = None
+    if rank == 0:
+        shared = {"version": RUN_STATE_VERSION, "next_epoch": int(next_epoch), "world": int(world), "meta": dict(meta or {}),
+                  "model": _cpu(model.state_dict()),
+                  "optimizer": None if optimizer is None else _cpu(optimizer.state_dict()),
+                  "optimizer_health": optimizer.health() if getattr(optimizer, "skip_nonfinite", False) else None,
+                  "scheduler": None if scheduler is None else _cpu(scheduler.state_dict()),
+                  "callbacks": [(type(cb).__name__, _cpu(cb.state_dict())) for cb in callbacks if hasattr(cb, "state_dict")]}
+    if world == 1:
+        _atomic_torch_save(dict(shared, **{k: per_rank[k] for k in ("rng", "loaders", "objects")}), path)
+        return
+    per_rank["buffers"] = _cpu(dict(model.named_buffers()))
+    _atomic_torch_save(per_rank, f"{path}.rank{rank}")  # the replica's part first: a shared part never points at a replica part that is older
+    if shared is not None:
+        _atomic_torch_save(shared, path)
+
+
+def load_run_state(path, rank=0, world=1) -> dict:
+    """The state `save_run_state` wrote, for `RunState(resume=...)`.  With `world > 1`: the shared part, then this rank's own file."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if state.get("version") != RUN_STATE_VERSION:
+        raise ValueError(f"{path}: run state version {state.get('version')}, this package reads {RUN_STATE_VERSION}")
+    if int(state["world"]) != int(world):
+        raise ValueError(f"{path} was written by a run of {state['world']} replica(s), this run has {world}: resuming with a different "
+                         "WORLD_SIZE is refused (the data streams and BatchNorm statistics are per replica)")
+    if world > 1:
+        own = torch.load(f"{path}.rank{rank}", map_location="cpu", weights_only=True)
+        if int(own["world"]) != int(world) or int(own["rank"]) != int(rank) or int(own["next_epoch"]) != int(state["next_epoch"]):
+            raise ValueError(f"{path}.rank{rank} (epoch {own['next_epoch']}, rank {own['rank']} of {own['world']}) does not belong to {path} "
+                             f"(epoch {state['next_epoch']}, {world} replicas)")
+        state.update({k: own[k] for k in ("rng", "loaders", "objects", "buffers")})
+    return state
+
+
+def _restore_run_state(state, model, optimizer, scheduler, callbacks, train_loader, val_loader, objects, rank=0):
+    """Put `state` into the live objects.  Called by fit() after the callbacks' on_train_start and before the first step (so before any
+    graph capture: the optimiser's load drops every cached device address)."""
+    model.load_state_dict(state["model"])
+    if "buffers" in state:  # this replica's own BatchNorm statistics over rank 0's
+        live = dict(model.named_buffers())
+        if set(live) != set(state["buffers"]):
+            raise ValueError("the run state's module buffers are not this model's")
+        with torch.no_grad():
+            for k, v in state["buffers"].items():
+                live[k].copy_(v)
+    if state["optimizer"] is not None:
+        if optimizer is None:
+            raise ValueError("the run state holds an optimiser state, fit() was given none")
+        optimizer.load_state_dict(state["optimizer"])
+    if state.get("optimizer_health") is not None:
+        if not getattr(optimizer, "skip_nonfinite", False):
+            raise ValueError("the run state was written with skip_nonfinite, this optimiser was built without")
+        optimizer.load_health(state["optimizer_health"])
+    if state["scheduler"] is not None:
+        if scheduler is None:
+            raise ValueError("the run state holds a scheduler state, fit() was given none")
+        scheduler.load_state_dict(state["scheduler"])
+    live_cbs = [cb for cb in callbacks if hasattr(cb, "state_dict")]
+    if rank != 0 and not live_cbs:
+        pass  # (the callbacks in the shared part are rank 0's: checkpoints and the SWA average are written there only)
+    elif [type(cb).__name__ for cb in live_cbs] != [n for n, _ in state["callbacks"]]:
+        raise ValueError(f"the run state holds callbacks {[n for n, _ in state['callbacks']]}, fit() was given {[type(cb).__name__ for cb in live_cbs]}")
+    for cb, (_, sd) in zip(live_cbs, state["callbacks"]):  # (zip: nothing to do on a rank without callbacks)
+        cb.load_state_dict(sd)
+    for what, live in (("loaders", _stateful({"train": train_loader, "val": val_loader})), ("objects", _stateful(dict(objects or {})))):
+        if set(live) != set(state[what]):
+            raise ValueError(f"the run state holds {what} {sorted(state[what])}, fit() was given {sorted(live)}")
+        for k, o in live.items():
+            o.load_state_dict(state[what][k])
+    _set_rng_state(state["rng"], _model_device(model))
+
+
 def fit(model: nn.Module, train_loader, criterions, optimizer, scheduler=None, epochs=1, callbacks=(), on_step=None,
-        grad_sync=None, val_loader=None, val_criterions=None, reducer=None, graphed=False):
+        grad_sync=None, val_loader=None, val_criterions=None, reducer=None, graphed=False, start_epoch=0, run_state: "RunState | None" = None,
+        max_consecutive_skips=10):
     """Epoch loop with Lightning's ordering: per step zero_grad -> forward -> loss -> backward -> (gradient exchange) -> clip + Adam;
     per epoch the scheduler step, then - when `val_loader` is given - a validation epoch (`validate`) whose value goes to the
     callbacks' `on_validation_end(epoch, model, val_loss)` (CheckpointCallback: best.ckpt / last.ckpt), then `on_train_epoch_end`.
@@ -1024,7 +1252,14 @@ def fit(model: nn.Module, train_loader, criterions, optimizer, scheduler=None, e
     `graphed=True` (single replica, ClipAdam): every step is a replay of ONE captured hipGraph (`GraphedTrainStep`; re-captured when the
     sub-batch layout or the epoch's loss weights change); `on_step` then receives the graph's static output tensors.
     `graphed="flat"`: the same with GraphedTrainStep's flat layout - one graph also when the per-Tag sizes change from step to step and
-    through the epochs of a weight ramp; `on_step` receives [B] loss vectors and their live-row masks ("mt_rows")."""
+    through the epochs of a weight ramp; `on_step` receives [B] loss vectors and their live-row masks ("mt_rows").
+    `start_epoch`: the loop runs `range(start_epoch, epochs)`.  `run_state` (RunState): after an epoch's callbacks (`on_train_epoch_end`
+    included) the run state is saved when due; with `run_state.resume` the saved state is restored after the callbacks' `on_train_start`
+    and before the first step, and the loop starts at the saved epoch.  Under TTK_DETERMINISTIC=1 the resumed run is bitwise the
+    uninterrupted one.  Epoch boundaries only: no signal handling, no mid-epoch resume.
+    `max_consecutive_skips` (ClipAdam(skip_nonfinite=True) only): once per epoch, after its last step, the optimiser's health counters are
+    read; new skips are reported with a RuntimeWarning, and NonFiniteGradientError names the culprit parameter once that many steps in a
+    row were skipped.  (10 is a policy, not a measurement.)"""
     stepper = None
     if graphed:
         if isinstance(graphed, str) and graphed != "flat":
@@ -1035,9 +1270,17 @@ def fit(model: nn.Module, train_loader, criterions, optimizer, scheduler=None, e
     for cb in callbacks:
         if hasattr(cb, "on_train_start"):
             cb.on_train_start(model)
+    if run_state is not None and run_state.resume is not None:
+        _restore_run_state(run_state.resume, model, optimizer, scheduler, callbacks, train_loader, val_loader, run_state.objects, run_state.rank)
+        saved_epoch = int(run_state.resume["next_epoch"])
+        if start_epoch not in (0, saved_epoch):
+            raise ValueError(f"fit: start_epoch={start_epoch}, the run state continues at epoch {saved_epoch}")
+        start_epoch = saved_epoch
     model.train()
     params = list(model.parameters()) if reducer is not None else None
-    for epoch in range(epochs):
+    guarded = bool(getattr(optimizer, "skip_nonfinite", False))
+    skipped_before = optimizer.health()["skipped"] if guarded else 0
+    for epoch in range(start_epoch, epochs):
         for batches in train_loader:
             if stepper is not None:
                 out = stepper.run(batches, epoch)
@@ -1061,6 +1304,8 @@ def fit(model: nn.Module, train_loader, criterions, optimizer, scheduler=None, e
             optimizer.step()
             if on_step is not None:
                 on_step(epoch, out)
+        if guarded:
+            skipped_before = _check_health(model, optimizer, epoch, skipped_before, max_consecutive_skips)
         if scheduler is not None:
             scheduler.step()
         if val_loader is not None:
@@ -1071,4 +1316,27 @@ def fit(model: nn.Module, train_loader, criterions, optimizer, scheduler=None, e
         for cb in callbacks:
             if hasattr(cb, "on_train_epoch_end"):
                 cb.on_train_epoch_end(epoch, model)
+        if run_state is not None and run_state.due(epoch + 1):
+            save_run_state(run_state.path, model, optimizer, scheduler, epoch + 1, callbacks, train_loader, val_loader, run_state.objects,
+                           run_state.meta, run_state.rank, run_state.world)
+            if run_state.stops(epoch + 1):
+                break
     return model
+
+
+def _check_health(model, optimizer, epoch, skipped_before, max_consecutive_skips):
+    """The once-per-epoch read of a guarded optimiser's device counters (fit)."""
+    h = optimizer.health()
+    if h["skipped"] == skipped_before:
+        return skipped_before
+    culprit = "?"
+    if h["culprit_index"] >= 0:
+        p = optimizer.parameter_at(h["culprit_index"])
+        culprit = next((n for n, q in model.named_parameters() if q is p), f"parameter {h['culprit_index']} of the optimiser")
+    if max_consecutive_skips is not None and h["consecutive"] >= max_consecutive_skips:
+        raise NonFiniteGradientError(f"epoch {epoch}: the last {h['consecutive']} optimiser steps had a non-finite gradient norm and were skipped "
+                                     f"({h['skipped']} in the run); first non-finite gradient of the most recent one: {culprit}")
+    import warnings
+    warnings.warn(f"epoch {epoch}: {h['skipped'] - skipped_before} optimiser step(s) skipped for a non-finite gradient norm ({h['skipped']} in the "
+                  f"run); first non-finite gradient of the most recent one: {culprit}", RuntimeWarning, stacklevel=3)
+    return h["skipped"]
