@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 35
+#define TTK_ABI_VERSION 36
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -819,6 +819,26 @@ int ttk_affine_labels(const float* tr, int B, int N, float* coord, float* pose, 
 int ttk_affine_labels2d(const float* tr, int B, int N, float* coord, float* pose, float* roi,
                         const float* pts_in, float* pts_out, const float* pts2d_in, float* pts2d_out,
                         ttk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (ABI 36) Ensemble reduction for pseudo-labelling (csrc/ensemble.hip; reference scripts/add_pose_pseudolabels.py:84-156 and
+ * neuralnets/torchquaternion.py:239-256 quat_average).  E networks (1 <= E <= 16) predicted the same B crops; member e's outputs sit in
+ * slot e of pose[E][B][4] (ijkw), coord[E][B][3], pts[E][B][68][3] (nullable), shape[E][B][S] (nullable, S <= 64), all in the crop's
+ * [-1, 1] coordinates as the network returns them.  back[B][2][3] maps normalised crop -> image pixels.  Per row b:
+ *   every member is mapped to image coordinates as ttk_affine_labels maps labels (the same device function: coord xy affine and size
+ *     times the scale, landmarks xy affine / z times sqrt|det| / flip map when det < 0, pose pre-multiplied by the in-plane rotation
+ *     atan2(-m01, m11), reversed under a mirror with j, k negated); shape has no geometry;
+ *   pose_out[B][4]  = quat_average of the transformed members: pivot = first argmax over components of sum_e |q_e|, members whose pivot
+ *                     component is < 0 negated, mean over e, divided by max(|mean|, FLT_MIN) (a zero mean gives zeros, never NaN);
+ *   coord_out[B][3], pts_out[B][68][3], shape_out[B][S] = arithmetic mean of the transformed members;
+ *   stats[B][5]     = mean_e geodesic angle (radians) between member e and pose_out; |mean| before the normalisation (the reference
+ *                     warns where it is <= 0.5); population standard deviation over e of coord x, y, size in pixels.
+ * pts / pts_out and shape / shape_out are given together or not at all (networks without the landmark head).  Every sum over members
+ * is serial in member order in one lane: results are bitwise repeatable in every mode.  One launch, no host synchronisation (graph
+ * capturable); E out of range, a missing required pointer or S out of range return -1 before anything is launched or written.
+ * ------------------------------------------------------------------------------------------- */
+int ttk_ensemble_reduce(const float* pose, const float* coord, const float* pts, const float* shape, const float* back, int E, int B,
+                        int S, float* pose_out, float* coord_out, float* pts_out, float* shape_out, float* stats, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Streaming probe (measurement infrastructure: bench.py `copy_probe`, tools/stream_sweep.py; no reference counterpart).

@@ -89,3 +89,79 @@ def load_resident_frames(path: str, tag, device="cuda", coord_convention_id: int
     fields = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in shard.items() if k != "image_size"}
     fields["coord_convention_id"] = torch.full((len(shard["image"]),), int(coord_convention_id), dtype=torch.int32, device=device)
     return ResidentFrames(tag, fields)
+
+
+# ---------------------------------------------------------------------------------------------
+# pseudo-labels (reference: scripts/add_pose_pseudolabels.py:131-156 writes them into the HDF5 file in place; a shard is rewritten)
+# ---------------------------------------------------------------------------------------------
+_LABEL_ARRAYS = {"pose": "quats", "coord": "coords", "pt3d_68": "pt3d_68", "shapeparam": "shapeparams"}  # Batch name -> HDF5 name
+_STAT_ARRAYS = {"rot_spread": "pseudolabel_rot_spread", "mean_quat_norm": "pseudolabel_mean_quat_norm", "coord_spread": "pseudolabel_coord_spread"}
+
+
+def write_pseudolabels(src: str, dst: str, labels: dict, keep=None, overwrite: bool = False) -> str:
+    """The shard `src` with the labels of an ensemble (eval.EnsemblePredictor) written to `dst` (may be `src`).
+
+    `labels`: Batch names -> arrays / tensors over ALL frames of `src`: "pose" [N,4] and "coord" [N,3] (image pixels, cell-centred as the
+    predictor returns them), optionally "pt3d_68" [N,68,3], "shapeparam" [N,S] and the statistics "rot_spread" [N], "mean_quat_norm" [N],
+    "coord_spread" [N,3].  They are stored under their HDF5 names (quats, coords, pt3d_68, shapeparams; the statistics as pseudolabel_*,
+    which decode_pose_shard does not read) with the half-pixel offset undone (- 0.5 on the xy of coord and pt3d_68), so that
+    decode_pose_shard(dst) returns what was passed in.  Every other array of the shard is copied untouched, image blobs byte for byte.
+    `keep`: boolean frame mask; dropped frames leave every per-frame array (the reference's filter_dataset.filter_file_by_frames) - like
+    it, a shard with `sequence_starts` is refused when frames are dropped.  Label arrays the shard already has, and an existing `dst`,
+    are replaced only with overwrite=True.  The write goes to a temporary file next to `dst`, then os.replace: no partial shard."""
+    import os
+    import tempfile
+
+    def host(v):
+        return np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v)
+
+    unknown = set(labels) - set(_LABEL_ARRAYS) - set(_STAT_ARRAYS)
+    if unknown or "pose" not in labels or "coord" not in labels:
+        raise ValueError(f"labels need 'pose' and 'coord' and may hold {sorted(set(_LABEL_ARRAYS) | set(_STAT_ARRAYS))}; got {sorted(labels)}")
+    with np.load(src) as d:
+        arrays = {k: d[k] for k in d.files}
+    if "image_lengths" in arrays:
+        n = len(arrays["image_lengths"])
+    elif "images" in arrays:
+        n = len(arrays["images"])
+    else:
+        raise ValueError(f"{src}: neither image_bytes/image_lengths nor images")
+    new = {}
+    for k, v in labels.items():
+        v = host(v).astype(np.float32)
+        if len(v) != n:
+            raise ValueError(f"labels[{k!r}] has {len(v)} rows, {src} has {n} frames")
+        if k in ("coord", "pt3d_68"):
+            v = v.copy()
+            v[..., :2] -= np.float32(0.5)
+        new[_LABEL_ARRAYS.get(k) or _STAT_ARRAYS[k]] = v
+    present = sorted(set(new) & set(arrays))
+    if not overwrite and (present or os.path.exists(dst)):
+        raise FileExistsError((f"{dst} exists" if os.path.exists(dst) else f"{src} already has {present}") + ": pass overwrite=True to replace")
+    if keep is not None:
+        keep = host(keep).astype(bool)
+        if keep.shape != (n,):
+            raise ValueError(f"keep has shape {keep.shape}, {src} has {n} frames")
+        if not keep.all() and "sequence_starts" in arrays:
+            raise ValueError(f"{src} has sequence_starts: frames of a sequence dataset cannot be dropped")
+    arrays.update(new)
+    if keep is not None and not keep.all():
+        if "image_bytes" in arrays:
+            lengths = arrays["image_lengths"].astype(np.int64)
+            offs = np.concatenate([[0], np.cumsum(lengths)])
+            blob = arrays.pop("image_bytes")
+            pieces = [blob[offs[i]:offs[i + 1]] for i in np.flatnonzero(keep)]
+            kept_blob = np.concatenate(pieces) if pieces else blob[:0]
+        arrays = {k: (v[keep] if v.ndim >= 1 and len(v) == n else v) for k, v in arrays.items()}
+        if "image_lengths" in arrays:
+            arrays["image_bytes"] = kept_blob
+    fd, tmp = tempfile.mkstemp(dir=os.path.dirname(os.path.abspath(dst)), prefix=".pseudolabels-", suffix=".npz")
+    try:
+        with os.fdopen(fd, "wb") as f:
+            np.savez(f, **arrays)
+        os.replace(tmp, dst)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    return dst

@@ -114,6 +114,70 @@ class Predictor:
         return metric.compute()
 
 
+class EnsemblePredictor(Predictor):
+    """Several networks on ONE crop, averaged on the device (reference: scripts/add_pose_pseudolabels.py:54-127, which runs a `Predictor`
+    per checkpoint - cropping every batch once per network - and averages on the host).  `predict_batch(images, rois)` takes what
+    `Predictor.predict_batch` takes, crops once, runs every network in eval mode on that crop into slot e of preallocated [E, B, ...]
+    buffers and reduces them with one launch of ttk_ensemble_reduce (csrc/ensemble.hip): every member is mapped to image coordinates as
+    `to_image_coordinates` maps it, then rotations are averaged with the reference's `quat_average` (neuralnets/torchquaternion.py:239-256)
+    and coord / pt3d_68 / shapeparam with the arithmetic mean.  Returns a Batch with pose [B,4], coord [B,3], pt3d_68 [B,68,3] and shapeparam
+    [B,S] (the last two only when EVERY network has the landmark head), and the agreement of the members: rot_spread [B] (mean geodesic
+    angle to the average, radians), mean_quat_norm [B] (length of the sign-aligned mean before normalisation; the reference warns where it
+    is <= 0.5), coord_spread [B,3] (population standard deviation of x, y, size in pixels).
+
+    Deliberate deviation from the reference script: it averages `unnormalized_quat`, which its Predictor does not transform back to image
+    coordinates (the script's own FIXME) and which networks built with --enable-6drot do not have.  Here the networks' `pose` (unit
+    quaternions) is averaged AFTER the back-transformation, so the average is a rotation in the image frame for every head type."""
+
+    def __init__(self, nets, focus_roi_expansion_factor: float = 1.2, device: str | torch.device = "cuda", resample: str = "bilinear"):
+        nets = list(nets)
+        if not 1 <= len(nets) <= 16:
+            raise ValueError(f"an ensemble has 1 to 16 networks, got {len(nets)}")
+        if len({n.input_resolution for n in nets}) != 1:
+            raise ValueError(f"the networks of an ensemble share one crop: input resolutions {[n.input_resolution for n in nets]} differ")
+        super().__init__(nets[0], focus_roi_expansion_factor, device, resample)
+        self._nets = [n.to(device).eval() for n in nets]
+        self._with_points = all(getattr(n, "enable_point_head", False) for n in self._nets)
+        self._buffers: dict = {}
+
+    def _slots(self, B: int, S: int) -> dict:
+        """[E, B, ...] input slots and the outputs of the reduction for one batch size (allocated once)."""
+        key = (B, S)
+        if key not in self._buffers:
+            E, f = len(self._nets), dict(dtype=torch.float32, device=self._device)
+            b = {"pose": torch.empty((E, B, 4), **f), "coord": torch.empty((E, B, 3), **f)}
+            if self._with_points:
+                b["pt3d_68"], b["shapeparam"] = torch.empty((E, B, 68, 3), **f), torch.empty((E, B, S), **f)
+            self._buffers[key] = b
+        return self._buffers[key]
+
+    @torch.no_grad()
+    def predict_batch(self, images, rois: Tensor) -> Batch:
+        _hip.lib().clear_stale_error("the start of an ensemble batch")
+        crop = self.crop_batch(images, rois)
+        x, B, N = crop["image"], int(rois.shape[0]), self.input_resolution
+        slots = None
+        for e, net in enumerate(self._nets):
+            preds = net(x)
+            if slots is None:
+                slots = self._slots(B, int(preds["shapeparam"].shape[-1]) if self._with_points else 0)
+            for k, buf in slots.items():
+                buf[e].copy_(preds[k])
+        back = (position_normalization(N, N).to(self._device) @ Affine2d(crop["image_transform"])).inv().tensor().contiguous()
+        f = dict(dtype=torch.float32, device=self._device)
+        out = {"pose": torch.empty((B, 4), **f), "coord": torch.empty((B, 3), **f)}
+        if self._with_points:
+            out["pt3d_68"], out["shapeparam"] = torch.empty((B, 68, 3), **f), torch.empty_like(slots["shapeparam"][0])
+        stats = torch.empty((B, 5), **f)
+        P = _hip.ptr
+        _hip.lib().call("ttk_ensemble_reduce", P(slots["pose"]), P(slots["coord"]), P(slots.get("pt3d_68")), P(slots.get("shapeparam")), P(back),
+                        len(self._nets), B, int(out["shapeparam"].shape[-1]) if self._with_points else 0, P(out["pose"]), P(out["coord"]),
+                        P(out.get("pt3d_68")), P(out.get("shapeparam")), P(stats))
+        out["rot_spread"], out["mean_quat_norm"], out["coord_spread"] = stats[:, 0], stats[:, 1], stats[:, 2:]
+        cats = {"coord": FieldCategory.xys, "pose": FieldCategory.quat, "pt3d_68": FieldCategory.points}
+        return Batch(Metadata(N, B, categories={k: c for k, c in cats.items() if k in out}), out)
+
+
 # ---------------------------------------------------------------------------------------------
 # metrics (reference :295-440)
 # ---------------------------------------------------------------------------------------------
