@@ -126,10 +126,6 @@ __global__ void __launch_bounds__(256) conv_prepare_repack_k(ConvPrepArgs a) {
   }
 }
 
-// gemm_mode() != GEMM_F16X2 is an experiment build running with TTK_GEMM=f32mfma: every entry point refuses it instead of switching kernels
-#define TTK_REQUIRE_CONV_F16(name) \
-  TTK_REQUIRE(gemm_mode() == GEMM_F16X2, name ": the ResNet convolutions exist on the fp16 kernels only (experiment build with TTK_GEMM=f32mfma?)")
-
 static bool conv_shape_ok(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
   return B > 0 && H > 0 && W > 0 && Cin >= 32 && Cin % 32 == 0 && Cout >= 64 && Cout % 64 == 0 && KH == KW && (KH == 1 || KH == 3) &&
          (stride == 1 || stride == 2) && pad == KH / 2;
@@ -143,7 +139,6 @@ extern "C" {
 
 int ttk_conv_weight_repack(const float* w, void* w_fwd, void* w_bwd, int Cout, int Cin, int KH, int KW, ttk_stream_t stream) {
   TTK_REQUIRE(w && (w_fwd || w_bwd) && Cout > 0 && Cin > 0 && KH > 0 && KW > 0, "conv_weight_repack: bad arguments");
-  TTK_REQUIRE_CONV_F16("conv_weight_repack");
   const int64_t n = (int64_t)Cout * Cin * KH * KW;
   float* hdr = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(w_fwd ? w_fwd : w_bwd) + 2 * n);  // behind the two planes
   launch_w16_absmax(w, n, hdr, (hipStream_t)stream);
@@ -158,7 +153,6 @@ int ttk_conv_prepare_weights(int n, const float* const* w, void* const* w_fwd, v
   for (int i = 0; i < n; ++i)
     TTK_REQUIRE(w[i] && (w_fwd[i] || w_bwd[i]) && cout[i] > 0 && cin[i] > 0 && cout[i] % 32 == 0 && cin[i] % 32 == 0 && (ksize[i] == 1 || ksize[i] == 3),
                 "conv_prepare_weights: bad tensor %d", i);
-  TTK_REQUIRE_CONV_F16("conv_prepare_weights");
   ConvPrepArgs a;
   a.n = n;
   int chunks = 0;
@@ -177,7 +171,6 @@ int ttk_conv_prepare_weights(int n, const float* const* w, void* const* w_fwd, v
 int ttk_conv_fwd(const float* a_in, const float* a_bound, const void* w_fwd, float* y, float* part, const float* pivot, int B, int H, int W,
                  int Cin, int Cout, int KH, int KW, int stride, int pad, ttk_stream_t stream) {
   TTK_REQUIRE(a_in && a_bound && w_fwd && y, "conv_fwd: null pointer");
-  TTK_REQUIRE_CONV_F16("conv_fwd");
   TTK_REQUIRE(conv_shape_ok(B, H, W, Cin, Cout, KH, KW, stride, pad), "conv_fwd: unsupported shape B=%d H=%d W=%d Cin=%d Cout=%d k=%d s=%d p=%d", B, H, W, Cin, Cout, KH, stride, pad);
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   const ConvGeom geo{H, W, Ho, Wo, stride, pad, KW, Cin, 0};
@@ -197,7 +190,6 @@ int ttk_conv_bwd_data(const float* g, const float* y, const float* bn, const voi
                       float* mask_bn, float* g_in, float* part, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                       int stride, int pad, ttk_stream_t stream) {
   TTK_REQUIRE(g && bn && w_bwd && g_in, "conv_bwd_data: null pointer");
-  TTK_REQUIRE_CONV_F16("conv_bwd_data");
   TTK_REQUIRE((mask_y == nullptr) == (mask_bn == nullptr), "conv_bwd_data: mask_y and mask_bn go together");
   TTK_REQUIRE(conv_shape_ok(B, H, W, Cin, Cout, KH, KW, stride, pad) && Cin % 64 == 0, "conv_bwd_data: unsupported shape");
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
@@ -215,7 +207,7 @@ int ttk_conv_bwd_data(const float* g, const float* y, const float* bn, const voi
 
 // dw[Cout][Cin][KH][KW] += sum_{pixels} dy (x) a_in.  The caller zeroes dw (or accumulates on purpose).
 size_t ttk_conv_wgrad_partial_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-  if (gemm_mode() != GEMM_F16X2 || !conv_shape_ok(B, H, W, Cin, Cout, KH, KW, stride, pad)) return 0;
+  if (!conv_shape_ok(B, H, W, Cin, Cout, KH, KW, stride, pad)) return 0;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   return conv_wgrad16_partial_bytes((int64_t)B * Ho * Wo, Cout, KH * KW * Cin, KH * KW);
 }
@@ -223,7 +215,6 @@ size_t ttk_conv_wgrad_partial_bytes(int B, int H, int W, int Cin, int Cout, int 
 int ttk_conv_bwd_weight(const float* g, const float* y, const float* bn, const float* a_in, const float* a_bound, float* dw, float* partial,
                         int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, ttk_stream_t stream) {
   TTK_REQUIRE(g && bn && a_in && a_bound && dw, "conv_bwd_weight: null pointer");
-  TTK_REQUIRE_CONV_F16("conv_bwd_weight");
   TTK_REQUIRE(conv_shape_ok(B, H, W, Cin, Cout, KH, KW, stride, pad), "conv_bwd_weight: unsupported shape");
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   const ConvGeom geo{H, W, Ho, Wo, stride, pad, KW, Cin, 0};

@@ -1,11 +1,8 @@
-// Shared between the pointwise-GEMM files (pwconv*.hip, pw_bwd_fused.hip) and conv.hip: operand / epilogue forms, the implicit-GEMM geometry,
-// the kernel-family switch and the layout of the prepared weight blocks.
+// Shared between the pointwise-GEMM files (pwconv*.hip, pw_bwd_fused.hip) and conv.hip: operand / epilogue forms, the implicit-GEMM geometry
+// and the layout of the prepared weight blocks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 namespace ttk {
 
@@ -29,21 +26,6 @@ struct ConvGeom {
   int Hs, Ws, Hg, Wg, stride, pad, KW, Kc, transposed;
   int par, nimg, ctile[4];
 };
-
-// TTK_GEMM=f32mfma (experiment builds) keeps every pointwise conv on v_mfma_f32_32x32x2_f32 (A/B timing and numerics comparisons); the ResNet18
-// convolutions exist in the fp16 form only and refuse that mode (conv.hip)
-enum { GEMM_F16X2 = 0, GEMM_F32 = 2 };
-inline int gemm_mode() {
-  static const int mode = [] {
-    const char* e = exp_env("TTK_GEMM");
-    if (e && strcmp(e, "f32mfma") == 0) return (int)GEMM_F32;
-    if (e && strcmp(e, "bf16x3") == 0)
-      fprintf(stderr, "libttk_hip: TTK_GEMM=bf16x3 (round 1's six-product bf16 split, csrc/pwconv_split.hip) was removed in round 3 - it is in the "
-                      "git history before the channel-block activation layout; using the fp16 kernels\n");
-    return (int)GEMM_F16X2;
-  }();
-  return mode;
-}
 
 // Layout of a prepared weight block of n = Cin * Cout elements (ttk_pwconv_prepare_weights): [forward operand][data-gradient operand]
 // [header: |w| maximum ...].  Every reader of the block takes the offsets from here.
@@ -85,8 +67,8 @@ bool f16r_gemm_shape(int K, int Nout, int dgrad);
 int f16r_partial_rows(int64_t M, int K, int Nout, int dgrad);
 int f16r_tile_rows(int64_t M, int K, int Nout, int dgrad);
 
-// pwconv_r.hip: weight gradient of the layers with Cin, Cout multiples of 256 on 256 x 256 tiles with transposed LDS fragment reads; always
-// reduces through `partial` (scratch of f16t_wgrad_scratch_bytes) and a fixed-order fold
+// pwconv_r.hip: weight gradient of the layers with Cin a multiple of 256 and Cout of 128 (but not 256 -> 256) on 128 (Cout) x 256 (Cin) tiles with
+// transposed LDS fragment reads; always reduces through `partial` (scratch of f16t_wgrad_scratch_bytes) and a fixed-order fold
 bool launch_f16t_wgrad(const float* g, const float* y, const float* bn_pw, const float* ydw, const float* bn_dw, float* dw, float* partial,
                        int64_t M, int Cin, int Cout, hipStream_t st);
 size_t f16t_wgrad_scratch_bytes(int64_t M, int Cin, int Cout);

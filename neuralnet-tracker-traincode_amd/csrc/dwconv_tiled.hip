@@ -83,7 +83,6 @@ inline DwTiling dw_tiling_sl(int B, int H, int W, int C, int stride, bool backwa
   t.SL = SL;
   t.NCT = 1;
   t.TW = Wo;
-  static const int col_tile = [] { const char* e = exp_env("TTK_DW_COLTILE"); return e ? atoi(e) : kColTile; }();  // (experiments)
   // Forward, images of several full-width bands (65 x 65, 33 x 33): the 3 - stride input rows two neighbouring bands share are staged
   // ONCE - a workgroup takes a contiguous run of bands and carries those rows over in LDS - so the tensor is read exactly once
   // (column tiles of 17 x 17 results staged 19 x 19 = 1.25 x; full-width bands without the carry 5 rows for 3 = 1.67 x; PMC of
@@ -91,13 +90,12 @@ inline DwTiling dw_tiling_sl(int B, int H, int W, int C, int stride, bool backwa
   // Backward (round 6): the same for the staged dy rows - neighbouring bands of input rows share 2 (stride 1) or 1 (stride 2) rows of dy - with
   // full-width bands instead of the 19 x 19 column tiles of the 65-pixel layers (halo 1.25 x on g and y) and the 10-for-8-row bands of the
   // 33-pixel ones.
-  static const int carry_bwd = [] { const char* e = exp_env("TTK_DW_CARRY_BWD"); return e ? atoi(e) : TTK_DW_CARRY_BWD; }();  // (experiments)
   // (stride 2, where the bands share ONE dy row of a tensor a quarter of the input's size, measured slower with the ring: 65 x 65 x 64 259 -> 268 us;
   // stride 1: 33 x 33 x 128 319 -> 284 us, 65 x 65 x 32 217 -> 190 us, profiles/r06_depthwise_backward_carry.txt)
-  t.carry = backward ? (carry_bwd && stride == 1 && (Wo + 2) <= 80)
+  t.carry = backward ? (TTK_DW_CARRY_BWD && stride == 1 && (Wo + 2) <= 80)
                      : (TTK_DW_CARRY && (3 - stride) * (W + 2) * (SL / 4) <= kCarryRegs * kBlock);
-  if (!t.carry && stride == 1 && W >= kColTileMinW && col_tile < W) {
-    t.NCT = (W + col_tile - 1) / col_tile;
+  if (!t.carry && stride == 1 && W >= kColTileMinW) {
+    t.NCT = (W + kColTile - 1) / kColTile;
     t.TW = (W + t.NCT - 1) / t.NCT;
   }
   const int Wtile = t.NCT > 1 ? t.TW : (backward ? Wo : W);

@@ -42,6 +42,7 @@ __global__ void __launch_bounds__(512) pw_bwd_fused_k(const float* __restrict__ 
                                                        float* __restrict__ wpartial, float* __restrict__ part, int64_t M, int ntiles) {
   using S = FusedShape<CIN, COUT>;
   constexpr int BM = kFusedBM, LDY = S::LDY, LDC = S::LDC, LDW = S::LDW, NTC = S::NTC, DG = S::DG, WG = S::WG;
+  // (instantiated for 32 -> 64 only: the 64 -> 128 layer, which the job split below also describes, runs on pw_bwd_fused16_k)
   static_assert((CIN == 32 && COUT == 64) || (CIN == 64 && COUT == 128), "shapes of the first two pointwise layers");
   // jobs per consumer wave: 32 -> 64: waves 0,1 one data-gradient tile each, waves 2,3 one weight-gradient tile each;
   // 64 -> 128: every wave one data-gradient tile and two weight-gradient tiles
@@ -778,19 +779,12 @@ pw_bwd_fused16w_k(const float* __restrict__ g, const float* __restrict__ y, cons
   }
 }
 
-// 128 -> 128, 128 -> 256 and 256 -> 256 always run on the fp16 pipe; 64 -> 128 too when the prepared block holds fp16 planes (default
-// TTK_GEMM mode), else on fp32 MFMA from the raw weights
-static bool fused_f16(int Cin) { return Cin == 128 || Cin == 256 || (Cin == 64 && gemm_mode() == GEMM_F16X2 && !exp_env("TTK_FUSED_FP32")); }
-// (experiment builds: TTK_FUSED_WIDE=0 routes both layers to the two kernels, =128 / =256 only that input width to the fused one)
-static bool fused_wide(int Cin, int Cout) {
-  static const int only = [] { const char* e = exp_env("TTK_FUSED_WIDE"); return e ? atoi(e) : -1; }();
-  return Cout == 256 && (Cin == 128 || Cin == 256) && (only < 0 || only == Cin);
-}
+// 32 -> 64 runs on fp32 MFMA from the raw weights; every other layer on the fp16 pipe from the prepared weight block
+static bool fused_f16(int Cin) { return Cin != 32; }
+static bool fused_wide(int Cin, int Cout) { return Cout == 256 && (Cin == 128 || Cin == 256); }
 constexpr int64_t kWideMaxM = ((int64_t)1 << 30) / 256 - kF16BM;  // 32-bit element offsets in pw_bwd_fused16w_k (past it: the two kernels)
 static bool fused_shape(int Cin, int Cout) {
-  // (the forms with 128 and more input channels take the |w| scale of the prepared weight block: default TTK_GEMM mode only)
-  return (Cin == 32 && Cout == 64) || (Cin == 64 && Cout == 128) ||
-         (((Cin == 128 && Cout == 128) || fused_wide(Cin, Cout)) && gemm_mode() == GEMM_F16X2);
+  return (Cin == 32 && Cout == 64) || (Cin == 64 && Cout == 128) || (Cin == 128 && Cout == 128) || fused_wide(Cin, Cout);
 }
 
 // workgroups that walk the row tiles = rows of `part` = slices of the deterministic weight gradient (256 -> 256 launches two
@@ -822,11 +816,11 @@ int ttk_pwconv1x1_bwd_fused(const float* g, const float* y, const float* bn_pw, 
   TTK_REQUIRE(g && y && bn_pw && ydw && bn_dw && g_dw && dw, "pwconv1x1_bwd_fused: null pointer");
   TTK_REQUIRE(fused_ok(M, Cin, Cout), "pwconv1x1_bwd_fused: only the 32 -> 64, 64 -> 128, 128 -> 128, 128 -> 256 and 256 -> 256 layers (got %d -> %d)", Cin, Cout);
   TTK_REQUIRE(((Cin == 128 && Cout == 128) || w) && (!fused_f16(Cin) || wsplit),
-              "pwconv1x1_bwd_fused: the fp16 forms (128 and more input channels; 64 -> 128 in the default mode) need the prepared weight block, all but 128 -> 128 the raw weights");
+              "pwconv1x1_bwd_fused: the fp16 forms (every layer but 32 -> 64) need the prepared weight block, all but 128 -> 128 the raw weights");
   const int ntiles = (int)ceil_div(M, fused_f16(Cin) ? kF16BM : kFusedBM), grid = fused_grid(M, Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   if (fused_f16(Cin)) {
-    // prepared block (ttk_pwconv_prepare_weights, fp16 mode): [forward planes 4n][data-gradient planes 4n][|w| maximum]
+    // prepared block (ttk_pwconv_prepare_weights): [forward planes 4n][data-gradient planes 4n][|w| maximum]
     const size_t n = (size_t)Cin * Cout;
     const unsigned char* ws = static_cast<const unsigned char*>(wsplit);
     const uint16_t* wq = reinterpret_cast<const uint16_t*>(ws + prep_bwd_offset(n));
@@ -839,10 +833,8 @@ int ttk_pwconv1x1_bwd_fused(const float* g, const float* y, const float* bn_pw, 
       hipLaunchKernelGGL((pw_bwd_fused16_k<128, 128>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, wq, w, wmx, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
     else
       hipLaunchKernelGGL((pw_bwd_fused16_k<64, 128>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, wq, w, wmx, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
-  } else if (Cin == 32) {
-    hipLaunchKernelGGL((pw_bwd_fused_k<32, 64>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, w, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
   } else {
-    hipLaunchKernelGGL((pw_bwd_fused_k<64, 128>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, w, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
+    hipLaunchKernelGGL((pw_bwd_fused_k<32, 64>), dim3(grid), dim3(512), 0, st, g, y, bn_pw, w, ydw, bn_dw, g_dw, dw, partial, part, M, ntiles);
   }
   if (partial) launch_fold_partials(partial, grid, (int64_t)Cin * Cout, dw, 1, st);
   TTK_LAUNCH_CHECK("pwconv1x1_bwd_fused");

@@ -375,9 +375,8 @@ static bool pw_shape_ok(int64_t M, int Cin, int Cout) {
 template <int MODE>
 static void launch_gemm(const float* A0, const float* A1, const float* bnA, const float* Bm, float* out, const float* E0,
                         const float* bnE, float* part, int64_t M, int K, int Nout, void* region, float* hdr, hipStream_t st) {
-  const int mode = gemm_mode();
-  if (mode == GEMM_F16X2 && launch_f16r_gemm<MODE>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return;
-  if (mode == GEMM_F16X2 && launch_f16_gemm<MODE>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return;
+  if (launch_f16r_gemm<MODE>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return;
+  if (launch_f16_gemm<MODE>(A0, A1, bnA, Bm, out, E0, bnE, part, M, K, Nout, region, hdr, st)) return;
   if (!Bm) Bm = static_cast<const float*>(region);  // prepared operand of a shape that stays on the fp32 kernels
   const dim3 blk(kBlock);
   const unsigned gm = (unsigned)ceil_div(M, BM);
@@ -400,7 +399,7 @@ struct PrepArgs {
   int cin[kPrepMax], cout[kPrepMax];
   int first_tile[kPrepMax + 1];  // 32x32 tiles of w, layer after layer
   int split_fwd[kPrepMax], split_bwd[kPrepMax];
-  int n, mode;
+  int n;
 };
 
 // element (row, k) of a [rows][K] operand: fp32 in place (split 0), or the two fp16 pieces of x * s (split16.h) in the planes of the
@@ -459,15 +458,12 @@ __global__ void __launch_bounds__(kBlock) pw_prepare_weights_k(PrepArgs a) {
   const float* w = a.w[l];
   unsigned char* fwd = a.out[l];
   unsigned char* bwd = a.out[l] + prep_bwd_offset(n);
-  float s = 1.f;
-  if (a.mode == GEMM_F16X2) {
-    static_assert(kPrepParts == kWave, "one value per lane");
-    float m = prep_parts(a, l)[threadIdx.x & 63];
+  static_assert(kPrepParts == kWave, "one value per lane");
+  float m = prep_parts(a, l)[threadIdx.x & 63];
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if (tile == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(a.out[l] + 8 * n) = m;  // the header the GEMMs take their scale from
-    s = pow2_scale(m);
-  }
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  if (tile == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(a.out[l] + 8 * n) = m;  // the header the GEMMs take their scale from
+  const float s = pow2_scale(m);
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += kBlock / 32) {
     const float x = w[(int64_t)(r0 + i) * Cin + c0 + tx];
@@ -535,18 +531,16 @@ static void fp32_wgrad_plan(int64_t M, int Cin, int Cout, int& bn, int& bk, int&
 }
 
 size_t ttk_pwconv_wgrad_scratch_bytes(int64_t M, int Cin, int Cout) {
-  if (!pw_shape_ok(M, Cin, Cout) || gemm_mode() != GEMM_F16X2) return 0;
+  if (!pw_shape_ok(M, Cin, Cout)) return 0;
   return f16t_wgrad_scratch_bytes(M, Cin, Cout);
 }
 
 size_t ttk_pwconv_wgrad_partial_bytes(int64_t M, int Cin, int Cout) {
   if (!pw_shape_ok(M, Cin, Cout)) return 0;
-  if (gemm_mode() == GEMM_F16X2) {
-    const size_t t = f16t_wgrad_scratch_bytes(M, Cin, Cout);
-    if (t) return t;
-    const size_t b = f16_wgrad_partial_bytes(M, Cin, Cout);
-    if (b) return b;
-  }
+  const size_t t = f16t_wgrad_scratch_bytes(M, Cin, Cout);
+  if (t) return t;
+  const size_t b = f16_wgrad_partial_bytes(M, Cin, Cout);
+  if (b) return b;
   int bn, bk, tiles;
   int64_t slices, rows;
   fp32_wgrad_plan(M, Cin, Cout, bn, bk, tiles, slices, rows);
@@ -559,8 +553,8 @@ int ttk_pwconv1x1_bwd_weight(const float* g, const float* y, const float* bn_pw,
   TTK_REQUIRE(pw_shape_ok(M, Cin, Cout), "pwconv1x1_bwd_weight: unsupported shape");
   TTK_REQUIRE_FP32_STORAGE(act_bf16, "pwconv1x1_bwd_weight");
   hipStream_t st = (hipStream_t)stream;
-  if (gemm_mode() == GEMM_F16X2 && (launch_f16t_wgrad(g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, st) ||
-                                    launch_f16_wgrad(g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, st))) {
+  if (launch_f16t_wgrad(g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, st) ||
+      launch_f16_wgrad(g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, st)) {
     TTK_LAUNCH_CHECK("pwconv1x1_bwd_weight");
   }
   int bn, bk, tiles;
@@ -598,7 +592,6 @@ int ttk_pwconv_prepare_weights(int n, const float* const* w, const int* cin, con
   TTK_REQUIRE(n > 0 && n <= kPrepMax && w && cin && cout && prepared, "pwconv_prepare_weights: bad arguments (1..16 layers)");
   PrepArgs a{};
   a.n = n;
-  a.mode = gemm_mode();
   int tiles = 0;
   for (int i = 0; i < n; ++i) {
     TTK_REQUIRE(w[i] && prepared[i] && pw_shape_ok(1, cin[i], cout[i]), "pwconv_prepare_weights: layer %d: null pointer or unsupported shape", i);
@@ -609,12 +602,12 @@ int ttk_pwconv_prepare_weights(int n, const float* const* w, const int* cin, con
     a.first_tile[i] = tiles;
     tiles += (cin[i] / 32) * (cout[i] / 32);
     // 0: fp32 rows; 1: piece planes [K/32][rows][32]; 2: the row-block kernels' planes [K/16][rows][16] (pwconv_r.hip)
-    a.split_fwd[i] = a.mode != GEMM_F16X2 ? 0 : f16r_gemm_shape(cin[i], cout[i], 0) ? 2 : f16_gemm_shape(cin[i], cout[i]);
-    a.split_bwd[i] = a.mode != GEMM_F16X2 ? 0 : f16r_gemm_shape(cout[i], cin[i], 1) ? 2 : f16_gemm_shape(cout[i], cin[i]);
+    a.split_fwd[i] = f16r_gemm_shape(cin[i], cout[i], 0) ? 2 : f16_gemm_shape(cin[i], cout[i]);
+    a.split_bwd[i] = f16r_gemm_shape(cout[i], cin[i], 1) ? 2 : f16_gemm_shape(cout[i], cin[i]);
   }
   a.first_tile[n] = tiles;
   hipStream_t st = (hipStream_t)stream;
-  if (a.mode == GEMM_F16X2) hipLaunchKernelGGL(pw_prepare_absmax_k, dim3(kPrepParts, n), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL(pw_prepare_absmax_k, dim3(kPrepParts, n), dim3(kBlock), 0, st, a);
   hipLaunchKernelGGL(pw_prepare_weights_k, dim3(tiles), dim3(kBlock), 0, st, a);
   TTK_LAUNCH_CHECK("pwconv_prepare_weights");
 }

@@ -1002,12 +1002,10 @@ bool launch_conv_gemm16(int amode, int emode, const float* A0, const float* A1, 
   do {                                                             \
     if (Nout % 256 == 0) TTK_CONV_LAUNCH(128, 256, AM_, EM_);      \
     else if (Nout % 128 == 0) TTK_CONV_LAUNCH(256, 128, AM_, EM_); \
-    else if (narrow) TTK_CONV_LAUNCH(128, 64, AM_, EM_);           \
-    else TTK_CONV_LAUNCH(256, 64, AM_, EM_);                       \
+    else TTK_CONV_LAUNCH(128, 64, AM_, EM_); /* 2 per CU */        \
     return true;                                                   \
   } while (0)
   if (Nout % 64 != 0 || geo.Kc % 32 != 0) return false;
-  static const bool narrow = !exp_env("TTK_CONV_WIDE64");  // 64 output channels: 128x64 tiles, two workgroups per CU (default) | 256x64
   if (amode == AMODE_PLAIN && emode == EMODE_STATS) TTK_CONV_TILES(AMODE_PLAIN, EMODE_STATS);
   if (amode == AMODE_BNGRAD && emode == EMODE_MASK) TTK_CONV_TILES(AMODE_BNGRAD, EMODE_MASK);
   if (amode == AMODE_BNGRAD && emode == EMODE_PLAIN) TTK_CONV_TILES(AMODE_BNGRAD, EMODE_PLAIN);

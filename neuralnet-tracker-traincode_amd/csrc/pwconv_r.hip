@@ -982,18 +982,15 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
 }
 
 // ---------------------------------------------------------------------------------------------
-// Weight gradient  dW[co][ci] += sum_m dy[m][co] * a[m][ci]  of the layers with Cin and Cout multiples of 256, 256 x 256 tiles.
+// Weight gradient  dW[co][ci] += sum_m dy[m][co] * a[m][ci]  of the layers with Cin a multiple of 256 and Cout of 128, 128 x 256 tiles.
 //
 // The contraction runs over the pixels m, so an MFMA fragment needs 8 CONSECUTIVE m of one channel, while memory has the channels
 // contiguous.  pw16_wgrad_k transposes in registers (4 rows x 4 channels per thread) and scatters 8-byte pieces into channel-major LDS
-// rows - 2-way bank conflicts on every store (SQ_LDS_BANK_CONFLICT = a third of its LDS cycles) and a 128 x 256 tile per CU, i.e.
-// every slice of dy is formed by two workgroups and every slice of a by four.  Here
+// rows - 2-way bank conflicts on every store (SQ_LDS_BANK_CONFLICT = a third of its LDS cycles).  Here
 //  * the producers store what they load: LDS holds the piece planes in the tensors' own [m][channel] order (8-byte pieces, lanes side by
 //    side: conflict-free), and the CONSUMERS read their fragments transposed with ds_read_b64_tr_b16 (a 4 m x 16 channel block per
 //    16-lane group, column-major into the lanes: the fragment of 32x32x16 is two such reads); rows are padded from 512 to 576 bytes so
 //    that the four rows of a block fall into four different 64-byte bank windows;
-//  * the tile is 256 x 256 on eight consumer waves (64 x 128 each): dy is formed twice (not per 128 output channels), a twice instead of
-//    four times;
 //  * every workgroup stores its tile to partial[slice][Cout][Cin] and wgrad_fold_k adds the slices in a fixed order: 64 MB of float
 //    atomics per launch would take 50 us at the chip's 1.3 TB/s atomic rate, the plain stores and the fold take about half - and the
 //    result is bitwise reproducible in every mode.
@@ -1013,154 +1010,13 @@ __device__ __forceinline__ f16x8 tr_frag(const unsigned char* plane, int off) {
 // 4 consecutive channels of one m-row: h at dst, l at dst + kTPlane
 __device__ __forceinline__ void tsplit_store(f32x4 v, unsigned char* dst) { split_store16(v, dst, kTPlane); }
 
-#if defined(TTK_EXPERIMENTS)  // (pw16t_wgrad_k is selectable by TTK_WGRAD_T=t only: ahead of pw16u_wgrad_k on no shape but 1024 x 1024, and there by 5 %)
-// G, Y: [M][Cout] (gradient w.r.t. the BatchNorm output, raw conv output), X: [M][Cin] (raw depthwise output); partial[slice][Cout][Cin]
-__global__ void __launch_bounds__(768) pw16t_wgrad_k(const float* __restrict__ G, const float* __restrict__ Y, const float* __restrict__ bn_pw,
-                                                     const float* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ partial,
-                                                     int64_t M, int Cin, int Cout, int64_t rows_per_slice) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kTRing];
-  const int tid = threadIdx.x;
-  // XCD-aware order: every XCD gets whole slices (the tiles of a slice read the same rows of g, y and x)
-  const unsigned NT = (Cout / 256) * (Cin / 256), NG = gridDim.x, Lid = blockIdx.x;
-  const unsigned xq = NG / 8, xr = NG % 8, xcd = Lid % 8;
-  const unsigned logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + Lid / 8;
-  const unsigned tile = logical % NT, slice = logical / NT;
-  const int tiles_k = Cin / 256;
-  const int n0 = (tile / tiles_k) * 256, k0 = (tile % tiles_k) * 256;  // first output channel / input channel of the tile
-  const int64_t m_begin = (int64_t)slice * rows_per_slice;
-  const int64_t m_end = (m_begin + rows_per_slice < M) ? m_begin + rows_per_slice : M;
-  const int nks = m_begin < m_end ? (int)((m_end - m_begin + 31) / 32) : 0;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const float sa = pow2_scale(bn_pw[(size_t)TTK_BN_AUX * Cout + TTK_AUX_DY_BOUND]);
-  const float sb = pow2_scale(bn_x[(size_t)TTK_BN_AUX * Cin + TTK_AUX_ACT_BOUND]);
-  f32x16 acc[2][4];  // consumer waves: 64 output channels x 128 input channels
-
-  if (wave >= 8) {
-    // ---------------- producers: wave w owns rows 8 w .. 8 w + 7 of every k32 step, lane = channel quad ----------------
-    __builtin_amdgcn_s_setprio(3);
-    const int pw = wave - 8, quad = tid & 63;
-    const int ca = n0 + 4 * quad, cb = k0 + 4 * quad;
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_GA * Cout + ca) * sa;
-    const f32x4 gb = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_GB * Cout + ca) * sa;
-    const f32x4 gmean = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_GMEAN * Cout + ca);
-    const f32x4 ymean = *reinterpret_cast<const f32x4*>(bn_pw + TTK_BN_MEAN * Cout + ca);
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(bn_x + TTK_BN_SCALE * Cin + cb) * sb;
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(bn_x + TTK_BN_MEAN * Cin + cb);
-    const f32x4 be = *reinterpret_cast<const f32x4*>(bn_x + TTK_BN_BETA * Cin + cb) * sb;
-    f32x4 rg[8], ry[8], rx[8];
-    const int64_t r0 = m_begin + 8 * pw;
-    // LDS: k16 stage (pw >> 1) of the step, rows 8 (pw & 1) .. + 7
-    unsigned char* wdy = lds + (pw >> 1) * kTStage + (8 * (pw & 1)) * kTRow + quad * 8;
-    unsigned char* wx = wdy + 2 * kTPlane;
-    auto load_row = [&](int ks, int i) {
-      int64_t row = r0 + (int64_t)ks * 32 + i;
-      row = row < m_end ? row : m_end - 1;  // (rows past the slice are zeroed when they are stored)
-      rg[i] = ld_act4(G + act_off(row, ca, M));
-      ry[i] = ld_act4(Y + act_off(row, ca, M));
-      rx[i] = ld_act4(X + act_off(row, cb, M));
-    };
-    auto store = [&](int ks) {  // the eight rows of step ks: BatchNorm backward / BatchNorm + ReLU, split, to LDS
-      unsigned char* dy = wdy + (ks & 1) * 2 * kTStage;
-      unsigned char* xx = wx + (ks & 1) * 2 * kTStage;
-      const int64_t row0 = r0 + (int64_t)ks * 32;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool live = row0 + i < m_end;  // rows past the slice contribute nothing
-        f32x4 v = ga * (rg[i] - gmean) + gb * (ry[i] - ymean);
-        f32x4 a = sc * (rx[i] - mu) + be;
-        a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
-        if (!live) { v = f32x4{0.f, 0.f, 0.f, 0.f}; a = v; }
-        tsplit_store(v, dy + i * kTRow);
-        tsplit_store(a, xx + i * kTRow);
-      }
-    };
-    if (nks > 0) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) load_row(0, i);
-      for (int s = 0; s < nks; ++s) {
-        store(s);
-        if (s + 1 < nks) {  // in flight across the barrier; waited for by the next store
-#pragma unroll
-          for (int i = 0; i < 8; ++i) load_row(s + 1, i);
-        }
-        rbarrier();  // stage s is in LDS; the consumers are done with stage s - 1
-      }
-      rbarrier();
-    }
-  } else {
-    // ---------------- consumers: transposed fragment reads + three piece products per block pair ----------------
-    const int lane = tid & 63, wm = wave >> 1, wn = wave & 1;
-    const int grp = lane >> 4, q = (lane & 15) >> 2, p4 = lane & 3, h = grp >> 1;
-    // this lane's address inside a plane for the 32-channel block that starts at channel `c32`: row 8h + q, channels c32 + 16 (grp & 1) + 4 p
-    const int lane_off = (8 * h + q) * kTRow + (16 * (grp & 1) + 4 * p4) * 2;
-    int aoff[2], boff[4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) aoff[i] = lane_off + (wm * 64 + i * 32) * 2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) boff[j] = 2 * kTPlane + lane_off + (wn * 128 + j * 32) * 2;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    if (nks > 0) {
-      rbarrier();  // stage 0 is in LDS
-      for (int it = 0; it < nks; ++it) {
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-          const unsigned char* S = lds + ((it & 1) * 2 + sub) * kTStage;
-          f16x8 a[2][2], b[2][2];
-#pragma unroll
-          for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i][pl] = tr_frag(S + pl * kTPlane, aoff[i]);
-            b[0][pl] = tr_frag(S + pl * kTPlane, boff[0]);
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int cur = j & 1;
-            if (j + 1 < 4) {
-#pragma unroll
-              for (int pl = 0; pl < 2; ++pl) b[cur ^ 1][pl] = tr_frag(S + pl * kTPlane, boff[j + 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[cur][1], acc[i][j], 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[cur][0], acc[i][j], 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[cur][0], acc[i][j], 0, 0, 0);
-            }
-          }
-        }
-        rbarrier();  // done with stage `it`; stage it + 1 is in LDS
-      }
-    }
-    // ---- the tile of this slice: plain stores (lanes = 32 consecutive input channels: 128-byte segments)
-    const float inv = 1.f / (sa * sb);
-    const int r = lane & 31, hh = lane >> 5;
-    float* dst = partial + (size_t)slice * Cout * Cin;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = n0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-          const int col = k0 + wn * 128 + j * 32 + r;
-          dst[(size_t)row * Cin + col] = acc[i][j][e] * inv;
-        }
-  }
-}
-
-#endif
-
 // ---------------------------------------------------------------------------------------------
-// The same weight gradient with the roles turned round: 128 (Cout) x 256 (Cin) tiles, FOUR consumer waves (64 x 128 each, one per
-// SIMD) and EIGHT producer waves with TWO register sets.  Both earlier forms wait for memory in their producers: the loads of a k32
-// step are issued, waited for (a round trip under load: 3-4 000 cycles), converted, and only then are the next ones issued - the
-// matrix pipe (1 536 cycles per step) idles two thirds of the time (SQ_WAIT_INST_ANY 59 %).  With eight producer waves a lane holds
-// 8 loads (128 B) per step instead of 24, so two steps fit into registers: the loads of steps s + 1 and s + 2 are in flight while
-// step s is converted.  LDS layout, transposed fragment reads and the partial-tile + fold epilogue are those of pw16t_wgrad_k.
+// pw16u_wgrad_k: 128 (Cout) x 256 (Cin) tiles, FOUR consumer waves (64 x 128 each, one per SIMD) and EIGHT producer waves with TWO
+// register sets.  The earlier forms (pw16_wgrad_k, and a 256 x 256 tile with eight consumer and four producer waves that is in the git
+// history: profiles/r03_wgrad_transposed.txt) wait for memory in their producers: the loads of a k32 step are issued, waited for (a round
+// trip under load: 3-4 000 cycles), converted, and only then are the next ones issued - the matrix pipe (1 536 cycles per step) idles two
+// thirds of the time (SQ_WAIT_INST_ANY 59 %).  With eight producer waves a lane holds 8 loads (128 B) per step instead of 24, so two
+// steps fit into registers: the loads of steps s + 1 and s + 2 are in flight while step s is converted.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(768) pw16u_wgrad_k(const float* __restrict__ G, const float* __restrict__ Y, const float* __restrict__ bn_pw,
                                                      const float* __restrict__ X, const float* __restrict__ bn_x, float* __restrict__ partial,
@@ -1256,10 +1112,11 @@ __global__ void __launch_bounds__(768) pw16u_wgrad_k(const float* __restrict__ G
       rbarrier();
     }
   } else {
-    // ---------------- consumers: transposed fragment reads + three piece products per block pair (as pw16t_wgrad_k) ----------------
+    // ---------------- consumers: transposed fragment reads + three piece products per block pair ----------------
     f32x16 acc[2][4];  // 64 output channels x 128 input channels
     const int lane = tid & 63, wm = wave >> 1, wn = wave & 1;
     const int grp = lane >> 4, q = (lane & 15) >> 2, p4 = lane & 3, h = grp >> 1;
+    // this lane's address inside a plane for the 32-channel block that starts at channel `c32`: row 8h + q, channels c32 + 16 (grp & 1) + 4 p
     const int lane_off = (8 * h + q) * kTRow + (16 * (grp & 1) + 4 * p4) * 2;
     int aoff[2], boff[4];
 #pragma unroll
@@ -1338,22 +1195,15 @@ __global__ void __launch_bounds__(256) wgrad_fold_k(const float* __restrict__ pa
   st4(dW + i, a);
 }
 
-// TTK_WGRAD_T: 0 = neither transposed-read kernel; t = pw16t_wgrad_k (256 x 256 tiles) where its tile divides the shape;
-// u (default) = pw16u_wgrad_k (128 x 256 tiles, eight producer waves) where its tile divides the shape
-static int t_wgrad_mode() {
-  static const int mode = [] { const char* e = exp_env("TTK_WGRAD_T"); return !e ? 2 : (e[0] == '0' ? 0 : (e[0] == 't' ? 1 : 2)); }();
-  return mode;
-}
-static bool t_wgrad_wide(int Cin, int Cout) { return t_wgrad_mode() == 1 && Cin % 256 == 0 && Cout % 256 == 0; }
+// pw16u_wgrad_k runs where its 128 x 256 tile divides the shape
 bool f16t_wgrad_shape(int Cin, int Cout) {
-  if (t_wgrad_mode() == 0 || gemm_mode() != GEMM_F16X2 || Cin < 256 || Cin % 256) return false;
-  if (t_wgrad_mode() == 1) return Cout >= 256 && Cout % 256 == 0;
+  if (Cin < 256 || Cin % 256) return false;
   // 256 x 256 (M = 147 968 at B = 512) is HBM-bound and has two tiles only - 128 slices of partial tiles: measured 126 us against
   // 121 us of pw16_wgrad_k; the others gain 9-20 % (profiles/r03_wgrad_transposed.txt)
   return Cout >= 128 && Cout % 128 == 0 && !(Cin == 256 && Cout == 256);
 }
 static void t_wgrad_plan(int64_t M, int Cin, int Cout, int& tiles, int64_t& slices, int64_t& rows) {
-  tiles = (Cout / (t_wgrad_wide(Cin, Cout) ? 256 : 128)) * (Cin / 256);
+  tiles = (Cout / 128) * (Cin / 256);
   slices = 256 / tiles;
   if (slices < 1) slices = 1;
   const int64_t max_slices = ceil_div(M, 64);
@@ -1374,27 +1224,18 @@ bool launch_f16t_wgrad(const float* g, const float* y, const float* bn_pw, const
   int tiles;
   int64_t slices, rows;
   t_wgrad_plan(M, Cin, Cout, tiles, slices, rows);
-#if defined(TTK_EXPERIMENTS)
-  if (t_wgrad_wide(Cin, Cout))
-    hipLaunchKernelGGL(pw16t_wgrad_k, dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
-  else
-#endif
-    hipLaunchKernelGGL(pw16u_wgrad_k, dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
+  hipLaunchKernelGGL(pw16u_wgrad_k, dim3((unsigned)(tiles * slices)), dim3(768), 0, st, g, y, bn_pw, ydw, bn_dw, partial, M, Cin, Cout, rows);
   const int64_t n = (int64_t)Cin * Cout;
   hipLaunchKernelGGL(wgrad_fold_k, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, st, partial, dw, n, (int)slices);
   return true;
 }
 
 // ---- tiling: row blocks of RT rows such that the tiles fill whole rounds of the CUs ------------------------------------------
-bool f16r_enabled() {
-  static const bool on = [] { const char* e = exp_env("TTK_GEMM_R"); return !(e && e[0] == '0'); }();
-  return on && gemm_mode() == GEMM_F16X2;
-}
 // Shapes [M][K] x [K][Nout] that run here.  The data gradient of the 256 -> 256 layer (K = Nout = 256, M = 147 968 at B = 512) is the one
 // measured slower than pw16_k's 128 x 256 tiles (147 vs 134 us: it is HBM-bound, and 193-row blocks only add epilogue time there).
 bool f16r_gemm_shape(int K, int Nout, int dgrad) {
-  if (!f16r_enabled() || K < 128 || K > 1024 || K % 32 != 0 || Nout < 256 || Nout % kRBN != 0) return false;
-  return !(dgrad && K == 256 && Nout == 256) || exp_env("TTK_R_ALL") != nullptr;
+  if (K < 128 || K > 1024 || K % 32 != 0 || Nout < 256 || Nout % kRBN != 0) return false;
+  return !(dgrad && K == 256 && Nout == 256);
 }
 
 struct RPlan { int rblk, rt, row_blocks; };
@@ -1402,15 +1243,11 @@ struct RPlan { int rblk, rt, row_blocks; };
 // and the time its bytes take through the CU (A rows from HBM at ~12 B/clk, 32 KB of weight planes from L2 at ~35 B/clk); the
 // epilogue writes (and, for the data gradient, reads) RT x 256 floats.
 static RPlan r_plan(int64_t M, int K, int Nout) {
-  const char* fe = exp_env("TTK_R_RBLK");  // experiment builds: 4 | 6 | 8 forces the tile's row blocks (anything else is ignored)
-  int force = fe ? atoi(fe) : 0;
-  if (force != 4 && force != 6 && force != 8) force = 0;
   static const int cus = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
   const int ct = Nout / kRBN, steps = K / 32;
   RPlan best{0, 0, 0};
   double best_cost = 1e300;
   for (int rblk = 4; rblk <= 8; rblk += 2) {
-    if (force && rblk != force) continue;
     const int RB = 32 * rblk;
     for (int r = 1; r <= 4096; ++r) {
       const int64_t rb = (int64_t)cus * r / ct;  // row blocks that fit into r rounds
@@ -1426,10 +1263,8 @@ static RPlan r_plan(int64_t M, int K, int Nout) {
       break;  // more rounds of smaller tiles only add per-tile overhead
     }
   }
-  if (best.rblk == 0) {  // (M beyond 4 096 rounds of full tiles: full-height tiles, as many rounds as it takes - never an empty grid)
-    const int rblk = force ? force : 8;
-    best = RPlan{rblk, 32 * rblk, (int)ceil_div(M, 32 * rblk)};
-  }
+  if (best.rblk == 0)  // (M beyond 4 096 rounds of full tiles: full-height tiles, as many rounds as it takes - never an empty grid)
+    best = RPlan{8, 256, (int)ceil_div(M, 256)};
   return best;
 }
 int f16r_partial_rows(int64_t M, int K, int Nout, int dgrad) { return f16r_gemm_shape(K, Nout, dgrad) ? r_plan(M, K, Nout).row_blocks : 0; }

@@ -29,6 +29,25 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
     assert lib.ttk_abi_version() == H.ABI_VERSION
 
 
+def test_library_has_no_kernel_selection_switches():
+    """The library reads one environment variable, TTK_DETERMINISTIC; the run-time A/B switches and the build flag that enabled them are gone."""
+    import glob
+
+    csrc = os.path.join(PKG, "csrc")
+    sources = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(sources) > 30
+    reads = [(os.path.basename(p), line) for p in sources for line in open(p).read().split("\n") if "getenv(" in line]
+    assert len(reads) == 1 and reads[0][1].count("getenv(") == 1 and "TTK_DETERMINISTIC" in reads[0][1], reads
+    for top in (csrc, os.path.join(REPO, "tools")):
+        for d, _, files in os.walk(top):
+            for f in files:
+                text = open(os.path.join(d, f), "rb").read()
+                if b"\0" in text:  # a built binary
+                    continue
+                for word in (b"exp_env", b"TTK_EXPERIMENTS"):
+                    assert word not in text, f"{word} in {os.path.join(d, f)}"
+
+
 @pytest.mark.parametrize("unc,pt", [(True, True), (False, True), (False, False)])
 def test_state_dict_inventory(unc, pt):
     from trackertraincode.neuralnets.models import NetworkWithPointHead

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Hardware counters of the pointwise GEMM kernels on the layer shapes (tools/bench_gemm.py), one rocprofv3 --pmc pass per counter set;
-#   bash tools/exp/pmc_gemm.sh <out dir>     (set TTK_GEMM_R=0 for the 128x256 kernels)
+#   bash tools/exp/pmc_gemm.sh <out dir>
 OUT=${1:-gpurun_out/pmc_gemm}
 R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$OUT
