@@ -482,7 +482,9 @@ int ttk_mobilenet_describe(const ttk_mobilenet_plan* plan, int backward, char* n
  * Dense convolutions of the ResNet18 backbone variant (backbones/resnet.py:52-104; arithmetic =
  * torchvision.models.resnet.BasicBlock/conv3x3/conv1x1, an un-vendored dependency of the reference) as implicit
  * GEMMs on the matrix cores.  Channels-last activations a[B][H][W][C] that are already post-BatchNorm/ReLU
- * ("materialised"); k in {1,3}, stride in {1,2}, pad = k/2; Cin % 32 == 0, Cout % 64 == 0.
+ * ("materialised"); k in {1,3}, stride in {1,2}, pad = k/2; Cin % 32 == 0, Cout % 64 == 0; any H, W >= 1 (need not be equal).
+ * ttk_conv_bwd_data has kernels for Cin % 64 == 0 only: Cin = 32, 96, ... is refused ("conv_bwd_data: unsupported shape") - a first
+ * layer's input needs no gradient.
  *   ttk_conv_weight_repack  w[Cout][Cin][KH][KW] -> w_fwd[.][KH*KW*Cin/32][Cout][32], w_bwd[.][KH*KW*Cout/32][Cin][32] (either may be
  *                           NULL; each a buffer of 3 * 2 bytes per weight): the 16-bit piece planes the GEMM producers
  *                           move without arithmetic - two fp16 planes of w * 2^s followed by a float header holding
@@ -522,11 +524,13 @@ int ttk_conv_bwd_weight(const float* g, const float* y, const float* bn, const f
 
 /* ---------------------------------------------------------------------------------------------
  * The non-GEMM kernels of the ResNet18 variant (backbones/resnet.py:52-104: torchvision ResNet18, 1-channel 7x7 stem).
- *   ttk_stem7_fwd          y[B][65][65][64] = conv7x7/s2/p3(x[B][1][H][W]) + part[ttk_partial_rows_elementwise(B*Ho*Wo*16)][2][64]
+ *   ttk_stem7_fwd          y[B][Ho][Wo][64] = conv7x7/s2/p3(x[B][1][H][W]), Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1 (H, W >= 7, need not
+ *                          be equal) + part[ttk_partial_rows_elementwise(B*Ho*Wo*16)][2][64]
  *   ttk_stem7_bwd_weight   dw[64][1][7][7] (overwritten) from dy = ga*(g-gmean)+gb*(y-mean); partial (nullable) = scratch of
  *                          ttk_stem7_wgrad_partial_bytes: workgroup partials folded in a fixed order instead of atomics
  *   ttk_maxpool3x3s2_fwd   a[B][Ho][Wo][C] = maxpool3x3/s2/p1(relu(bn(y))), idx = window position of the first maximum;
- *                          raises bn[TTK_BN_AUX][TTK_AUX_ACT_BOUND] to max a
+ *                          raises bn[TTK_BN_AUX][TTK_AUX_ACT_BOUND] to max a.  H, W >= 2 (a single row or column is refused, forward
+ *                          and backward); C a power of two in [32, 1024]
  *   ttk_maxpool3x3s2_bwd   g[B][H][W][C] = gradient w.r.t. bn(y) (ReLU mask applied) from ga (+ gb) w.r.t. the pooled
  *                          activation; part[ttk_partial_rows_elementwise(B*H*W*C/4)][2][C] = (sum g, sum g*(y-mean))
  *   ttk_bn_add_act         a = relu(bn(y) + r); r = res, or res_bn(res) when res is the raw downsample-conv output
@@ -538,6 +542,8 @@ int ttk_conv_bwd_weight(const float* g, const float* y, const float* bn, const f
  *   ttk_bn_bwd_apply       dy = ga*(g-gmean) + gb*(y-mean), materialised once for a convolution's two gradients in the form
  *                          the fp16-split GEMMs consume: dy[2][rows][C] fp16 = h = fp16(dy*2^s), l = fp16(dy*2^s - h) with
  *                          2^s * bn[TTK_BN_AUX][TTK_AUX_DY_BOUND] in [2^14, 2^15) (4 bytes per element, like fp32)
+ *                          C a power of two in [32, 1024], as for every elementwise kernel of this group: a convolution with
+ *                          Cout = 192 has no producer of this form here (its gradients take g, y, bn)
  *   ttk_residual_bwd       gs = (ga (+ gb)) * [a > 0]; part = sums for bn(y); partd (with yd, bnd) = sums for the
  *                          downsample BatchNorm; rows of both = ttk_partial_rows_elementwise(rows*C/4).  Raises
  *                          TTK_AUX_GMAX of bn (and bnd) to max |gs|.

@@ -1,6 +1,7 @@
 """GPU parity of the implicit-GEMM convolution entry points (ResNet18 variant) against float64 torch convolutions
 on the host.  Inputs are channels-last activations, exactly as the backbone stores them.  The operand magnitude bounds
-the fp16-split kernels scale by (include/ttk.h, row TTK_BN_AUX) are given with some slack, as the training step's are."""
+the fp16-split kernels scale by (include/ttk.h, row TTK_BN_AUX) are given with some slack, as the training step's are.
+Geometry off the square path (H != W, even sides, empty parity classes) and per-row accuracy: tests/test_conv_rows_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -17,20 +17,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_ref import floor_abs as _floor, pow2_scale as _pow2_scale  # shared with the per-row convolution tests
+
 pytestmark = pytest.mark.gpu
 BN_SCALE, BN_BETA, BN_MEAN, BN_RSTD, BN_GA, BN_GB, BN_GMEAN, BN_AUX = range(8)
 AUX_ACT_BOUND, AUX_DY_BOUND, AUX_GMAX = range(3)
 PROBES = (10, 20, 30, 36)  # probe row i holds elements of magnitude 2^-PROBES[i] x the bound
-
-
-def _pow2_scale(bound):
-    return 2.0 ** (14 - int(np.floor(np.log2(float(bound)))))
-
-
-def _floor(x, bound):
-    """absolute error floor of every element of x under the split with `bound`: 0 where all 22 bits are kept"""
-    S = _pow2_scale(bound)
-    return np.where(np.abs(x) * S >= 2.0 ** -3, 0.0, 2.0 ** -25 / S)
 
 
 def _chain32(a, b_t):
