@@ -218,12 +218,19 @@ int ttk_dwconv3x3_bwd_data_rawskip(const float* g_dw, const float* y_dw, const f
 /* ---------------------------------------------------------------------------------------------
  * Pointwise 1x1 conv = GEMM on the matrix cores - DepthWiseBlock.conv_sep, mobilenet_v1.py:67,82.
  *   y[M][Cout] = a_dw[M][Cin] . w[Cout][Cin]^T,   a_dw = max(bn_dw(ydw), 0) on load,  M = B*Ho*Wo
- * Compute-bound shapes run as split-operand products on the 16-bit matrix pipe with fp32-chain accuracy: two fp16
- * pieces per operand and three products (csrc/split16.h, csrc/pwconv_f16.hip).  The HBM-bound early layers run on
- * v_mfma_f32_32x32x2_f32 (experiment builds, TTK_GEMM=f32mfma: every layer).  The fp16 form needs the operand bounds of row TTK_BN_AUX: bn_dw[AUX][ACT_BOUND] (forward, weight
- * gradient), bn_pw[AUX][DY_BOUND] (both gradients).
+ * Which kernel runs a shape [M][K] x [Nout][K]^T (forward: K = Cin, Nout = Cout; data gradient: K = Cout, Nout = Cin) is decided by the
+ * shape alone (tests/pw_ref.py restates it; tests/test_pw_rows_gpu.py holds every form to float64 row by row):
+ *  - split-operand products on the 16-bit matrix pipe with fp32-chain accuracy - two fp16 pieces per operand and three products
+ *    (csrc/split16.h) - for K >= 64 and Nout = 128 or a multiple of 256: the row-block kernels of csrc/pwconv_r.hip for K >= 128 and
+ *    Nout a multiple of 256 (all but the data gradient of 256 -> 256), pw16_k of csrc/pwconv_f16.hip for the rest;
+ *  - v_mfma_f32_32x32x2_f32 (exact fp32 products, csrc/pwconv.hip: pw_gemm_k) for everything else (K = 32; Nout = 32 or 64) and for
+ *    EVERY shape when wsplit == NULL.
+ * The weight gradient runs split for Cin, Cout >= 128 (pw16u_wgrad_k / pw16_wgrad_k) and on fp32 MFMA (pw_wgrad_k) when either is below.
+ * The split forms need the operand bounds of row TTK_BN_AUX: bn_dw[AUX][ACT_BOUND] (forward, weight gradient), bn_pw[AUX][DY_BOUND]
+ * (both gradients); the fp32 forms do not read them.
  * wsplit (forward and data gradient): scratch of ttk_pwconv_prepared_bytes(Cin, Cout) for the split weight operand,
- * or a block that ttk_pwconv_prepare_weights filled (then w / wt == NULL); NULL selects the fp32 MFMA kernels.
+ * or a block that ttk_pwconv_prepare_weights filled (then w / wt == NULL); NULL selects the fp32 MFMA kernels, which write
+ * ttk_partial_rows_gemm(M) rows of `part` whatever the shape (ttk_partial_rows_pwconv answers for the kernel that runs WITH wsplit).
  * ------------------------------------------------------------------------------------------- */
 int ttk_pwconv1x1_fwd(const float* ydw, const float* bn_dw, const float* w, float* y, float* part, const float* pivot,
                       int64_t M, int Cin, int Cout, void* wsplit, int act_bf16, ttk_stream_t stream);
@@ -235,9 +242,9 @@ int ttk_pwconv1x1_bwd_data(const float* g, const float* y, const float* bn_pw, c
 /* dw[Cout][Cin] += dy^T . a_dw.  dw must be zeroed (or hold the running gradient) before the call.
  * partial == NULL: the M dimension is split over workgroups that add atomically (fp32 atomics: the result depends on
  * the order the hardware commits them).  partial = scratch of ttk_pwconv_wgrad_partial_bytes(M, Cin, Cout) (0 = this
- * shape / GEMM mode has no such form): every slice of M stores its tile and a second kernel adds the slices to dw in a
+ * shape has no such form: 32 -> 32, whose single tile four waves share through atomics - scratch passed there is ignored): every slice of M stores its tile and a second kernel adds the slices to dw in a
  * fixed order - bitwise reproducible.  For Cin, Cout multiples of 256 the slice form is also the FASTER one (256 x 256 tiles with transposed
- * LDS reads, csrc/pwconv_r.hip): ttk_pwconv_wgrad_scratch_bytes says how much scratch the default mode wants to be handed as `partial`
+ * LDS reads, csrc/pwconv_r.hip): ttk_pwconv_wgrad_scratch_bytes says how much scratch the entry point wants to be handed as `partial`
  * for a shape (0: none, the atomic form runs). */
 size_t ttk_pwconv_wgrad_partial_bytes(int64_t M, int Cin, int Cout);
 size_t ttk_pwconv_wgrad_scratch_bytes(int64_t M, int Cin, int Cout);
@@ -252,8 +259,8 @@ int ttk_pwconv1x1_bwd_weight(const float* g, const float* y, const float* bn_pw,
  * storage) in one kernel: g, y and ydw are read once instead of twice (these layers are HBM-bound).  32 -> 64 runs on the fp32 matrix pipe
  * from the raw weights w[Cout][Cin] (wsplit unused); 128 -> 128 on the fp16 pipe from the block that
  * ttk_pwconv_prepare_weights filled (wsplit; w unused), with the operand bounds of row TTK_BN_AUX; 64 -> 128 on the fp16
- * pipe too in the default TTK_GEMM mode (w AND wsplit: the raw weights, cut in the kernel with the block's |w| scale),
- * on fp32 MFMA otherwise; 128 -> 256 and 256 -> 256 (default TTK_GEMM mode only, M * 256 < 2^30) on the fp16 pipe, w AND wsplit as
+ * pipe too (w AND wsplit: the raw weights, cut in the kernel with the block's |w| scale);
+ * 128 -> 256 and 256 -> 256 (M * 256 < 2^30) on the fp16 pipe, w AND wsplit as
  * 64 -> 128 (256 -> 256 runs two workgroups per row tile, 128 input channels each).  dw accumulates
  * (fp32 atomics per workgroup, or - partial = scratch of ttk_pwconv1x1_bwd_fused_partial_bytes - workgroup rows folded in a
  * fixed order); g_dw and part as ttk_pwconv1x1_bwd_data, with ttk_pwconv1x1_bwd_fused_rows(M, Cin, Cout) partial rows

@@ -544,6 +544,7 @@ size_t ttk_pwconv_wgrad_partial_bytes(int64_t M, int Cin, int Cout) {
   int bn, bk, tiles;
   int64_t slices, rows;
   fp32_wgrad_plan(M, Cin, Cout, bn, bk, tiles, slices, rows);
+  if (bn == 32 && bk == 32) return 0;  // four waves share the one 32 x 32 tile: no slice store, the launcher keeps the atomics
   return (size_t)slices * Cin * Cout * sizeof(float);
 }
 
@@ -560,6 +561,7 @@ int ttk_pwconv1x1_bwd_weight(const float* g, const float* y, const float* bn_pw,
   int bn, bk, tiles;
   int64_t slices, rows;
   fp32_wgrad_plan(M, Cin, Cout, bn, bk, tiles, slices, rows);
+  TTK_REQUIRE(bn < 128 || bk < 128, "pwconv1x1_bwd_weight: no fp32 form for Cin, Cout >= 128");
   const dim3 grid(tiles, (unsigned)slices), blk(kBlock);
   // deterministic mode: every slice of M owns partial[slice][Cout][Cin]; the two waves that share an output tile in the
   // WS = 2 variants add into a ZEROED slot (a + b = b + a: still reproducible); four-wave sharing (32 x 32) is not
@@ -568,8 +570,8 @@ int ttk_pwconv1x1_bwd_weight(const float* g, const float* y, const float* bn_pw,
   if (partial && shared) (void)hipMemsetAsync(partial, 0, (size_t)slices * Cin * Cout * sizeof(float), st);
 #define TTK_WG(BN_, BK_, WR_, WC_, WS_) \
   hipLaunchKernelGGL((pw_wgrad_k<BN_, BK_, WR_, WC_, WS_>), grid, blk, 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows)
-  if (bn == 128 && bk == 128) TTK_WG(128, 128, 2, 2, 1);
-  else if (bn == 128 && bk == 64) TTK_WG(128, 64, 2, 2, 1);
+  // (128 x 128 never arrives: channel counts are powers of two, so Cin, Cout >= 128 is an f16_wgrad_shape and has returned above)
+  if (bn == 128 && bk == 64) TTK_WG(128, 64, 2, 2, 1);
   else if (bn == 128 && bk == 32) TTK_WG(128, 32, 4, 1, 1);
   else if (bn == 64 && bk == 128) TTK_WG(64, 128, 2, 2, 1);
   else if (bn == 64 && bk == 64) TTK_WG(64, 64, 2, 2, 1);
