@@ -179,6 +179,10 @@ int ttk_stem_bwd_weight(const void* g, const void* y, const float* bn, const flo
  *                                                 (bn + relu (+ residual), mobilenet_v1.py:79-90 / :162-163)
  * a_out (nullable): materialise a_in, needed when THIS block has a residual connection
  * (mobilenet_v1.py:70,86-88).  w is the reference's weight (C,1,3,3) as is.
+ * Shapes: C a power of two in 32..1024, W <= 256, stride 1 | 2; the stride-2 FORWARD additionally W <= 163 (a band of it stages three
+ * full-width input rows in LDS, 3 (W + 2) 128 + 2048 bytes, and a workgroup has 64 KiB).  Every other shape returns -1 from the argument
+ * checks, before anything is launched or written, and ttk_partial_rows_dwconv returns -1 for it.  The data gradient takes W <= 256 at
+ * either stride.
  * ------------------------------------------------------------------------------------------- */
 int ttk_dwconv3x3_fwd(const float* yprev, const float* bn_prev, const float* skip_prev, float* a_out,
                       const float* w, float* y, float* part, const float* pivot, int B, int H, int W, int C,

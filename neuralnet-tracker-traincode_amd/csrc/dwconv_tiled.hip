@@ -606,6 +606,17 @@ static bool dw_shape_ok2(int B, int H, int W, int C, int stride) {
   return B > 0 && H > 0 && W > 0 && W <= 256 && C >= 32 && C <= 1024 && (C & (C - 1)) == 0 && (stride == 1 || stride == 2);
 }
 
+// Dynamic LDS of the forward kernel: the stage + [4][2][SL] doubles of reduction scratch.  dw_band_rows clamps R up to 1 AFTER the pixel
+// budget is spent, so a stride-2 image too wide for the carry and for column tiles (stride 1 only) stages 3 full-width rows whatever
+// they cost: 3 (W + 2) 128 + 2048 bytes, past the 64 KiB a launch gets without raising hipFuncAttributeMaxDynamicSharedMemorySize from
+// W = 164.  No network reaches that (the widest stride-2 layer is 65 wide); the shapes are refused (ttk.h) rather than given a path of
+// one workgroup per CU that nothing has measured.  (The backward stays under 52 KiB for every W <= 256.)
+constexpr size_t kMaxDynLds = 64 * 1024;
+static size_t dw_fwd_lds_bytes(const DwTiling& t, int W) {
+  const size_t stage = (size_t)t.NI * t.stage_rows * ((t.NCT > 1 ? t.TW : W) + 2) * t.SL;
+  return (stage + 16 * t.SL) * sizeof(float);
+}
+
 }  // namespace ttk
 
 using namespace ttk;
@@ -614,7 +625,9 @@ extern "C" {
 
 int ttk_partial_rows_dwconv(int B, int H, int W, int C, int stride, int backward) {
   if (!dw_shape_ok2(B, H, W, C, stride)) return -1;
-  return dw_tiling(B, H, W, C, stride, backward != 0).rows;
+  const DwTiling t = dw_tiling(B, H, W, C, stride, backward != 0);
+  if (!backward && dw_fwd_lds_bytes(t, W) > kMaxDynLds) return -1;  // stride-2 forward, W > 163: refused (ttk.h)
+  return t.rows;
 }
 
 // ttk_dwconv3x3_fwd and ttk_dwconv3x3_fwd_rawskip (raw = the residual operand is a raw convolution output + skip_bn)
@@ -627,8 +640,9 @@ static int dw_fwd_launch(const char* name, bool raw, const float* yprev, const f
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const DwTiling t = dw_tiling(B, H, W, C, stride, false);
   TTK_REQUIRE((int64_t)((B + t.NI - 1) / t.NI) * t.nbands * t.NCT < ((int64_t)1 << 31), "%s: too many tiles for 32-bit indexing", name);
-  const size_t stage = (size_t)t.NI * t.stage_rows * ((t.NCT > 1 ? t.TW : W) + 2) * t.SL;
-  const size_t sm = (stage + 16 * t.SL) * sizeof(float);  // + [4][2][SL] doubles of reduction scratch
+  const size_t sm = dw_fwd_lds_bytes(t, W);
+  TTK_REQUIRE(sm <= kMaxDynLds, "%s: unsupported shape W=%d stride=%d: the stage of %zu bytes exceeds the 64 KiB of LDS of a workgroup (stride-2 forward: W <= 163)",
+              name, W, stride, sm);
   // the specialisation <stride 1 | 2, residual input (none | stored | raw), slab = kCB, carry mode>
   with_flag(stride == 2, [&](auto s2) {
     with_flag(t.carry != 0, [&](auto carry) {

@@ -27,30 +27,31 @@ def _nchw(t):  # [B,H,W,C] -> [B,C,H,W]
     return t.permute(0, 3, 1, 2)
 
 
-# (B, H, W, C, stride, skip)
+# (B, H, W, C, stride, skip).  The path each case takes TODAY, forward | backward, as tests/dw_ref.py: expected_path restates dw_tiling
+# (tests/test_dw_ref.py pins the 50-, 70- and 78-wide cases as carried bands and 79 as the first width with column tiles).  A workgroup
+# "walks" when a slab has more tiles than its 768 / (C / 32) workgroups; only then does a carried band take rows over from another.
 SHAPES = [(4, 9, 9, 64, 1, True),     # 3 images per tile, ragged last tile
           (5, 5, 5, 32, 1, False),    # 5x5: all images in one tile
           (9, 5, 5, 64, 1, True),     # 7 + 2 images
-          (2, 50, 50, 32, 1, False),  # column tiles, last one narrower
-          (2, 40, 70, 32, 1, True),   # non-square, bands and column tiles
-          (2, 65, 65, 32, 1, False),  # the network's first layer
-          (3, 33, 33, 64, 1, True),   # row bands only
-          (2, 33, 33, 64, 2, False),  # stride 2, odd size
-          (3, 10, 12, 32, 2, False),  # stride 2, even sizes
-          (6, 9, 9, 128, 2, False),   # stride 2, several images per tile
-          (1, 17, 17, 256, 1, True),
-          # more bands than resident workgroups: a workgroup of the forward walks CONSECUTIVE bands of an image and carries their
-          # shared input rows over in LDS (round 4), across image boundaries too; a_out rows are stored by whoever stages them
-          (40, 65, 65, 32, 1, True),
-          (40, 65, 65, 32, 2, False),
-          (100, 33, 33, 64, 1, True),
-          (90, 33, 33, 64, 2, False),
-          # round 6: the BACKWARD walks consecutive full-width bands too (stride 1, staged width <= 80: a ring of LDS rows keeps the dy rows
-          # two bands share) - the lean form (no residual operands) across image boundaries, and images too wide for it (column tiles stay)
-          (40, 65, 65, 32, 1, False),
-          (3, 30, 90, 32, 1, True),
-          (2, 20, 100, 64, 1, False),
-          (7, 78, 78, 32, 1, True)]    # staged width exactly 80
+          (2, 50, 50, 32, 1, False),  # full-width carried bands (R = 5, 10 bands), one tile per workgroup: no row is handed on
+          (2, 40, 70, 32, 1, True),   # non-square; full-width carried bands (R = 3, 14 bands, the last of 1 row), one tile per workgroup
+          (2, 65, 65, 32, 1, False),  # the network's first layer: carried bands (R = 3, 22 bands), one tile per workgroup
+          (3, 33, 33, 64, 1, True),   # carried bands (R = 8, 5 bands), one tile per workgroup
+          (2, 33, 33, 64, 2, False),  # stride 2, odd size: carried bands forward (R = 4) | one band per image
+          (3, 10, 12, 32, 2, False),  # stride 2, even sizes: 2 | 3 images per tile
+          (6, 9, 9, 128, 2, False),   # stride 2, several images per tile (3 | 6)
+          (1, 17, 17, 256, 1, True),  # one band, one image per tile
+          # more tiles than resident workgroups: a workgroup walks CONSECUTIVE bands of an image and hands their shared rows on (forward:
+          # registers, round 4; backward, stride 1: the LDS ring, round 6); a_out rows are stored by whoever stages them
+          (40, 65, 65, 32, 1, True),   # 880 tiles on 768 workgroups: runs of two, none across an image boundary
+          (40, 65, 65, 32, 2, False),  # 680 | 200 tiles: one per workgroup, nothing walks
+          (100, 33, 33, 64, 1, True),  # 500 tiles on 384 workgroups: walks, across image boundaries too
+          (90, 33, 33, 64, 2, False),  # forward 450 tiles on 384 workgroups: walks across image boundaries | one band per image, 90 tiles
+          (40, 65, 65, 32, 1, False),  # the lean backward on the walking ring
+          # images too wide for the carry (staged width > 80, i.e. W >= 79): column tiles in both directions
+          (3, 30, 90, 32, 1, True),    # 6 column tiles of 15, 2 bands (19 + 11 rows)
+          (2, 20, 100, 64, 1, False),  # 6 column tiles of 17 (the last 15 wide), 2 bands (17 + 3 rows)
+          (7, 78, 78, 32, 1, True)]    # staged width exactly 80: the widest carried bands (R = 2, 39 bands), one tile per workgroup
 
 
 @pytest.mark.parametrize("B,H,W,C,stride,skip", SHAPES)
