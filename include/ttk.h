@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 36
+#define TTK_ABI_VERSION 37
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -856,6 +856,49 @@ int ttk_affine_labels2d(const float* tr, int B, int N, float* coord, float* pose
  * ------------------------------------------------------------------------------------------- */
 int ttk_ensemble_reduce(const float* pose, const float* coord, const float* pts, const float* shape, const float* back, int E, int B,
                         int S, float* pose_out, float* coord_out, float* pts_out, float* shape_out, float* stats, ttk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (ABI 37) Closed-loop tracking on the device (csrc/track.hip; reference scripts/evaluate_stability.py:248-264 closed_loop_tracking, which
+ * crops every frame around the box predicted on the previous one, clamped to the image, and reads that box back to the host per frame).
+ * L lanes (1 <= L <= 16) are independent trackers that share one network and advance in lockstep: lane l follows sequence lane_seq[l]
+ * (int32) of the resident frame stack frames[S][T][Hs][Ws] (uint8 with src_is_u8, else float32; grey levels) with the crop enlargement
+ * lane_factor[l].  Device state: roi_state[L][4], the current boxes (x0, y0, x1, y1 in pixels), and the int32 *t_dev, the current frame
+ * index - on the device so that a captured graph can advance it.  One frame = ttk_track_crop, the network, ttk_track_update; neither call
+ * synchronises, uses atomics or reads anything on the host (graph capturable), and two runs are bitwise equal.
+ *   ttk_track_crop    one launch instead of the crop's three.  With t = *t_dev, per lane:
+ *                       view_roi[l] (int32 [L][4]) = ttk_view_roi of roi_state[l], scale lane_factor[l], translation (0, 0) (for which
+ *                                                    the result does not depend on beyond_border_shift);
+ *                       tr[l] ([L][2][3])          = ttk_roi_transform of it with a null `angles`;
+ *                       out[l] ([L][1][N][N])      = ttk_affine_warp of frame (lane_seq[l], t) under tr[l], times mul plus add;
+ *                     all three BITWISE what the three launches give (the same device functions, csrc/crop_math.h).  Neither *t_dev nor
+ *                     roi_state is written.  t outside [0, T): nothing is written; a lane whose lane_seq is outside [0, S) writes nothing.
+ *   ttk_track_update  one launch (one workgroup, one wave per lane) instead of the back-transformation and the host's clamp.  roi[L][4],
+ *                     coord[L][3], pose[L][4] (ijkw), pts[L][68][3] (nullable): the network's outputs for the L crops, in the crop's
+ *                     [-1, 1] coordinates; tr: what ttk_track_crop wrote.  With t = *t_dev, per lane:
+ *                       back = (norm(N) o tr[l])^-1 in closed form, norm(N): x -> x 2 / N - 1  (eval.Predictor.to_image_coordinates);
+ *                       row t of traj_roi[T][L][4], traj_coord[T][L][3], traj_pose[T][L][4], traj_pts[T][L][68][3] (nullable with pts) =
+ *                         the outputs under `back`, mapped as ttk_affine_labels maps labels (the same device function: mirrored and
+ *                         rotated tr are covered although the tracker only produces axis-aligned ones);
+ *                       traj_roi_in[t][l] = roi_state[l] before the update: the box the frame was cropped with;
+ *                       candidate = (max(0, x0), max(0, y0), min(x1, Ws), min(y1, Hs)) of the back-transformed box (reference :257-259);
+ *                       it is VALID iff the four back-transformed values are finite (tested before the clamp), w = x1 - x0 > 0 and
+ *                         h = y1 - y0 > 0 hold for the candidate AND for the network's own box roi[l] (the back-transformed box is the
+ *                         bounding box of four corners, which would re-sort an inverted prediction), and max(w, h) lane_factor[l] >= 2
+ *                         of the candidate (the next integer view box is then at least one pixel wide and the next tr finite);
+ *                       valid: roi_state[l] = candidate, lost[t][l] (uint8 [T][L]) = 0; otherwise roi_state[l] stays - the lane crops the
+ *                         next frame around its last good box - and lost[t][l] = 1; the frame's predictions are written either way.
+ *                         (A deliberate deviation: the reference has no rule, a box that leaves the image gives it a negative width and
+ *                         garbage from then on.)
+ *                     After a workgroup barrier *t_dev = t + 1.  t outside [0, T): nothing is written and the counter stays.
+ * Both return -1 before anything is launched or written when L is outside [1, 16], a required pointer is null, a size is not positive
+ * (crop: or N > 4096), or (update) pts and traj_pts are not given together.  Area-filtered resampling (ttk_area_crop) has no fused form.
+ * ------------------------------------------------------------------------------------------- */
+int ttk_track_crop(const void* frames, int src_is_u8, int S, int T, int Hs, int Ws, const int* lane_seq, const float* lane_factor,
+                   const float* roi_state, const int* t_dev, int L, int N, float mul, float add, int* view_roi, float* tr, float* out,
+                   ttk_stream_t stream);
+int ttk_track_update(const float* roi, const float* coord, const float* pose, const float* pts, const float* tr, int* t_dev, int L, int N,
+                     int T, int Hs, int Ws, const float* lane_factor, float* roi_state, float* traj_roi_in, float* traj_roi,
+                     float* traj_coord, float* traj_pose, float* traj_pts, unsigned char* lost, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Streaming probe (measurement infrastructure: bench.py `copy_probe`, tools/stream_sweep.py; no reference counterpart).

@@ -10,6 +10,8 @@
 //   roi -> tr  : center_rotation(angle) @ range_remap(view_roi -> [0,N]^2)            (:159-177)
 //   warp       : out[b,0,i,j] = bilinear(src_b, tr^-1 (j+.5, i+.5) - .5) * mul + add   (gather-bound)
 //   labels     : coord / pose / roi / pt3d_68 / pt2d_68 under tr, then under the [0,N] -> [-1,1] normalisation
+// The per-sample arithmetic of the first three is in crop_math.h, shared with the fused crop of the closed-loop tracker (track.hip).
+#include "crop_math.h"
 #include "head_math.h"
 #include "label_math.h"
 #include "ttk_common.h"
@@ -20,19 +22,7 @@ __global__ void view_roi_k(const float* __restrict__ roi, const float* __restric
                            int B, int* __restrict__ out) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const float x0 = roi[4 * b], y0 = roi[4 * b + 1], x1 = roi[4 * b + 2], y1 = roi[4 * b + 3];
-  const float rx = t[2 * b], ry = t[2 * b + 1];
-  const float bw = __fsub_rn(x1, x0), bh = __fsub_rn(y1, y0);
-  const float cx = __fmul_rn(0.5f, __fadd_rn(x1, x0)), cy = __fmul_rn(0.5f, __fadd_rn(y1, y0));
-  const float size = __fmul_rn(fmaxf(bw, bh), f[b]);
-  const float wx = __fadd_rn(__fmul_rn(0.5f, fabsf(__fsub_rn(size, bw))), __fmul_rn(bbs, fminf(size, bw)));
-  const float wy = __fadd_rn(__fmul_rn(0.5f, fabsf(__fsub_rn(size, bh))), __fmul_rn(bbs, fminf(size, bh)));
-  const float tx = __fmul_rn(wx, rx), ty = __fmul_rn(wy, ry);
-  const float hs = __fmul_rn(size, 0.5f);
-  out[4 * b + 0] = (int)rintf(__fadd_rn(__fsub_rn(cx, hs), tx));
-  out[4 * b + 1] = (int)rintf(__fadd_rn(__fsub_rn(cy, hs), ty));
-  out[4 * b + 2] = (int)rintf(__fadd_rn(__fadd_rn(cx, hs), tx));
-  out[4 * b + 3] = (int)rintf(__fadd_rn(__fadd_rn(cy, hs), ty));
+  view_roi_row(roi + 4 * b, f[b], t[2 * b], t[2 * b + 1], bbs, out + 4 * b);
 }
 
 // tr = unnorm(N) @ rot(angle) @ norm(N) @ remap(view_roi -> [0,N]^2), row-major 2x3
@@ -40,21 +30,7 @@ __global__ void roi_transform_k(const int* __restrict__ vr, const float* __restr
                                 float* __restrict__ tr) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const float x0 = (float)vr[4 * b], y0 = (float)vr[4 * b + 1], x1 = (float)vr[4 * b + 2], y1 = (float)vr[4 * b + 3];
-  const float sx = (float)N / (x1 - x0), sy = (float)N / (y1 - y0);
-  const float ox = -x0 * sx, oy = -y0 * sy;  // remap
-  const float a = angles ? angles[b] : 0.f, c = cosf(a), s = sinf(a), h = 0.5f * (float)N;
-  // p -> (p - h)/h -> R -> *h + h   ==  R p + (h - R h)
-  const float r00 = c, r01 = -s, r10 = s, r11 = c;
-  const float t0 = h - (r00 * h + r01 * h), t1 = h - (r10 * h + r11 * h);
-  float* m = tr + 6 * b;
-  m[0] = r00 * sx; m[1] = r01 * sy; m[2] = r00 * ox + r01 * oy + t0;
-  m[3] = r10 * sx; m[4] = r11 * sy; m[5] = r10 * ox + r11 * oy + t1;
-}
-
-template <typename T>
-__device__ __forceinline__ float fetch(const T* img, int H, int W, int y, int x) {
-  return (x >= 0 && x < W && y >= 0 && y < H) ? (float)img[(size_t)y * W + x] : 0.f;
+  roi_transform_row(vr + 4 * b, angles, b, N, tr + 6 * b);
 }
 
 // one thread per output pixel; consecutive lanes = consecutive output columns (coalesced store, gather load)
@@ -65,20 +41,7 @@ __global__ void __launch_bounds__(kBlock) affine_warp_k(const T* __restrict__ sr
   const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (idx >= (int64_t)B * N * N) return;
   const int j = (int)(idx % N), i = (int)((idx / N) % N), b = (int)(idx / ((int64_t)N * N));
-  const float* m = tr + 6 * b;
-  const float det = m[0] * m[4] - m[1] * m[3];
-  const float inv = 1.f / det;
-  const float px = (float)j + 0.5f - m[2], py = (float)i + 0.5f - m[5];
-  const float u = (m[4] * px - m[1] * py) * inv - 0.5f;
-  const float v = (-m[3] * px + m[0] * py) * inv - 0.5f;
-  const float fu = floorf(u), fv = floorf(v);
-  const int x0 = (int)fu, y0 = (int)fv;
-  const float ax = u - fu, ay = v - fv;
-  const T* img = src + (size_t)b * Hs * Ws;
-  const float v00 = fetch(img, Hs, Ws, y0, x0), v01 = fetch(img, Hs, Ws, y0, x0 + 1);
-  const float v10 = fetch(img, Hs, Ws, y0 + 1, x0), v11 = fetch(img, Hs, Ws, y0 + 1, x0 + 1);
-  const float val = (v00 * (1.f - ax) + v01 * ax) * (1.f - ay) + (v10 * (1.f - ax) + v11 * ax) * ay;
-  out[idx] = fmaf(val, mul, add);
+  out[idx] = warp_pixel(src + (size_t)b * Hs * Ws, Hs, Ws, tr + 6 * b, i, j, mul, add);
 }
 
 // one wave per sample: labels under tr[b], then (N > 0) under the pixel -> [-1,1] normalisation

@@ -113,6 +113,186 @@ class Predictor:
             metric.update(preds, targets)
         return metric.compute()
 
+    @torch.no_grad()
+    def predict_cropped_normalized_batch(self, images: Tensor) -> Batch:
+        """The network on crops that are already cut out, scaled to [B,1,N,N] and whitened (what `crop_batch` returns as "image");
+        nothing is transformed back: the predictions stay in the crop's [-1, 1] coordinates (reference :228-243)."""
+        if self._device.type == "cuda":
+            _hip.lib().clear_stale_error("the start of an evaluation batch")
+        preds = dict(self._net(images.to(self._device)))
+        cats = {"coord": FieldCategory.xys, "pose": FieldCategory.quat, "pt3d_68": FieldCategory.points}
+        return Batch(Metadata(int(images.shape[-1]), int(images.shape[0]), categories={k: c for k, c in cats.items() if k in preds}), preds)
+
+    def evaluate_cropped_normalized(self, metric, batches):
+        """`batches`: iterable of Batches (or dicts) with "image" = normalised crops and the labels the metric reads, in the crop's
+        coordinates (reference :245-252)."""
+        for batch in batches:
+            metric.update(self.predict_cropped_normalized_batch(batch["image"]), batch)
+        return metric.compute()
+
+
+# ---------------------------------------------------------------------------------------------
+# closed-loop tracking (reference: scripts/evaluate_stability.py:229-264)
+# ---------------------------------------------------------------------------------------------
+TRACK_MAX_LANES = 16  # kTrackMaxLanes of csrc/track.hip
+
+
+def track_box_is_valid(roi, factor: float, width: int, height: int) -> bool:
+    """The validity rule of ttk_track_update (include/ttk.h) in float32: finite, and after the reference's clamp to the image w > 0, h > 0
+    and max(w, h) * factor >= 2."""
+    r = np.asarray(roi, dtype=np.float32)
+    if not np.all(np.isfinite(r)):
+        return False
+    x0, y0 = np.maximum(np.float32(0), r[0]), np.maximum(np.float32(0), r[1])
+    x1, y1 = np.minimum(r[2], np.float32(width)), np.minimum(r[3], np.float32(height))
+    w, h = np.float32(x1 - x0), np.float32(y1 - y0)
+    return bool(w > 0 and h > 0 and np.float32(np.maximum(w, h) * np.float32(factor)) >= 2)
+
+
+class ClosedLoopTracker:
+    """A network run over a video in closed loop (reference scripts/evaluate_stability.py:248-264): every frame is cropped around the box
+    the network predicted on the previous frame, clamped to the image.  The loop-carried state - the current box of every lane and the
+    frame counter - lives on the device: a frame is ttk_track_crop -> `net(crop)` in eval mode -> ttk_track_update (csrc/track.hip), no
+    host read of anything until the last frame is enqueued, one synchronisation at the end.
+
+    `track(frames, first_rois, lanes=None)`: frames uint8 or float32 [T,H,W] or [S,T,H,W] (grey levels; S equally sized videos, moved to
+    the device once), first_rois [S,4] the box of frame 0 of every video, lanes a list of (sequence, factor) - independent trackers that
+    share the network and advance in lockstep, 1 to 16 of them; default every sequence x every factor of the constructor, sequence-major.
+    Returns a Batch, everything in image pixels as `Predictor.predict_batch` returns it: roi_in [T,L,4] (the box each frame was cropped
+    with), roi [T,L,4], coord [T,L,3], pose [T,L,4], pt3d_68 [T,L,68,3] (networks with the landmark head), lost [T,L] (bool), and
+    lane_seq [L] / lane_factor [L].
+
+    The `lost` rule (a deliberate deviation: the reference has none - a box that leaves the image gives it a negative width and garbage
+    from then on): the clamped predicted box becomes the next frame's box only if its four values are finite, the network's own box and
+    the clamped one have a positive width and height, and max(w, h) * factor >= 2; otherwise lost[t, l] is set, the frame's predictions are still recorded, and the lane crops
+    the next frame around its last good box.
+    Not in closed loop: area-filtered resampling (ttk_area_crop has no fused form: `resample="area"` is refused) and the uncertainty
+    outputs (`pose_scales_tril`, `coord_scales`), which are not recorded.
+
+    graphed=True captures crop -> forward -> update once (after a warm-up frame on scratch state) and replays the graph T times; the
+    device counter selects the frame.  A single-stream, linear graph; bitwise the eager trajectory."""
+
+    def __init__(self, net: torch.nn.Module, factors=(1.0, 1.2), device: str | torch.device = "cuda", graphed: bool = False,
+                 resample: str = "bilinear"):
+        if resample != "bilinear":
+            raise ValueError(f"ClosedLoopTracker: resample={resample!r} is not available in closed loop - the fused crop (ttk_track_crop) "
+                             "samples bilinearly; ttk_area_crop takes a host-side image base pointer and has no fused form")
+        self._net = net.to(device).eval()
+        self._device = torch.device(device)
+        self._factors = tuple(float(f) for f in factors)
+        self._graphed = bool(graphed)
+        self._mul, self._add = 1.0 / 256.0, -0.5  # whitening of GpuFocusRoiAugment, as Predictor crops
+
+    @property
+    def input_resolution(self) -> int:
+        return self._net.input_resolution
+
+    def _frame(self, st: dict) -> None:
+        """Enqueues one frame: crop, forward, update.  No host read."""
+        L, N = st["L"], st["N"]
+        P, call = _hip.fast_ptr, _hip.lib().call
+        S, T, Hs, Ws = st["frames"].shape
+        call("ttk_track_crop", P(st["frames"]), st["u8"], S, T, Hs, Ws, P(st["lane_seq"]), P(st["lane_factor"]), P(st["roi_state"]), P(st["t"]),
+             L, N, self._mul, self._add, P(st["view"]), P(st["tr"]), P(st["crop"]))
+        preds = self._net(st["crop"])
+        if "roi" not in preds:
+            raise ValueError(f"ClosedLoopTracker: the network {type(self._net).__name__} has no box head output ('roi'): closed-loop "
+                             f"tracking crops every frame around the predicted box (outputs: {sorted(preds)})")
+        # named: the buffers must outlive the enqueue of the kernel that reads them
+        st["keep"] = outs = [preds[k].to(torch.float32).contiguous() for k in ("roi", "coord", "pose")]
+        pts = preds["pt3d_68"].to(torch.float32).contiguous() if st["traj_pts"] is not None else None
+        outs.append(pts)
+        call("ttk_track_update", P(outs[0]), P(outs[1]), P(outs[2]), P(pts), P(st["tr"]), P(st["t"]), L, N, T, Hs, Ws, P(st["lane_factor"]),
+             P(st["roi_state"]), P(st["roi_in"]), P(st["roi"]), P(st["coord"]), P(st["pose"]), P(st["traj_pts"]), P(st["lost"]))
+
+    @torch.no_grad()
+    def track(self, frames, first_rois, lanes=None) -> Batch:
+        dev = self._device
+        frames = torch.as_tensor(frames)
+        if frames.dim() == 3:
+            frames = frames[None]
+        if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"ClosedLoopTracker.track: frames are uint8 or float32 [T,H,W] or [S,T,H,W], got {frames.dtype} {tuple(frames.shape)}")
+        S, T, Hs, Ws = (int(v) for v in frames.shape)
+        first = torch.as_tensor(first_rois, dtype=torch.float32).reshape(-1, 4).cpu()
+        if first.shape[0] != S:
+            raise ValueError(f"ClosedLoopTracker.track: first_rois has {first.shape[0]} boxes for {S} sequences")
+        if lanes is None:
+            lanes = [(s, f) for s in range(S) for f in self._factors]
+        lanes = [(int(s), float(f)) for s, f in lanes]
+        L = len(lanes)
+        if not 1 <= L <= TRACK_MAX_LANES:
+            raise ValueError(f"ClosedLoopTracker.track: 1 to {TRACK_MAX_LANES} lanes (sequence x factor), got {L}")
+        for i, (s, f) in enumerate(lanes):
+            if not 0 <= s < S:
+                raise ValueError(f"ClosedLoopTracker.track: lane {i} follows sequence {s}, but there are {S}")
+            if not track_box_is_valid(first[s].numpy(), f, Ws, Hs):
+                raise ValueError(f"ClosedLoopTracker.track: the first box {first[s].tolist()} of sequence {s} is not a valid start for lane {i} "
+                                 f"(factor {f}) on {Ws} x {Hs} frames: finite, inside the image with positive width and height, max(w, h) * factor >= 2")
+        if T < 1:
+            raise ValueError("ClosedLoopTracker.track: no frames")
+        _hip.lib().clear_stale_error("the start of a closed-loop track")  # once per track, not once per frame
+        N = self.input_resolution
+        f32 = dict(dtype=torch.float32, device=dev)
+        lane_seq = torch.tensor([s for s, _ in lanes], dtype=torch.int32, device=dev)
+        lane_factor = torch.tensor([f for _, f in lanes], **f32)
+        start = first[[s for s, _ in lanes]].to(dev).contiguous()
+        with_pts = bool(getattr(self._net, "enable_point_head", False))
+        st = {"L": L, "N": N, "frames": frames.to(dev).contiguous(), "u8": int(frames.dtype == torch.uint8), "lane_seq": lane_seq,
+              "lane_factor": lane_factor, "roi_state": start.clone(), "t": torch.zeros((), dtype=torch.int32, device=dev),
+              "view": torch.empty((L, 4), dtype=torch.int32, device=dev), "tr": torch.empty((L, 2, 3), **f32),
+              "crop": torch.empty((L, 1, N, N), **f32), "roi_in": torch.zeros((T, L, 4), **f32), "roi": torch.zeros((T, L, 4), **f32),
+              "coord": torch.zeros((T, L, 3), **f32), "pose": torch.zeros((T, L, 4), **f32),
+              "traj_pts": torch.zeros((T, L, 68, 3), **f32) if with_pts else None, "lost": torch.zeros((T, L), dtype=torch.uint8, device=dev)}
+        if self._graphed:
+            self._replay(st, start, T)
+        else:
+            for _ in range(T):
+                self._frame(st)
+        torch.cuda.synchronize(dev)  # the one synchronisation
+        if int(st["t"].item()) != T:
+            raise RuntimeError(f"ClosedLoopTracker.track: the device counter stands at {int(st['t'].item())} after {T} frames")
+        out = {"roi_in": st["roi_in"], "roi": st["roi"], "coord": st["coord"], "pose": st["pose"], "lost": st["lost"].bool(),
+               "lane_seq": lane_seq, "lane_factor": lane_factor}
+        if with_pts:
+            out["pt3d_68"] = st["traj_pts"]
+        cats = {"coord": FieldCategory.xys, "pose": FieldCategory.quat, "pt3d_68": FieldCategory.points, "roi": FieldCategory.roi,
+                "roi_in": FieldCategory.roi}
+        return Batch(Metadata(N, T, categories={k: c for k, c in cats.items() if k in out}), out)
+
+    def _replay(self, st: dict, start: Tensor, T: int) -> None:
+        """One warm-up frame on a side stream (its writes - row 0, the state, the counter - are undone), one capture of a frame, T replays."""
+        with _hip.CAPTURE_LOCK:
+            side = torch.cuda.Stream(device=self._device)
+            side.wait_stream(torch.cuda.current_stream(self._device))
+            with torch.cuda.stream(side):
+                self._frame(st)
+                st["roi_state"].copy_(start)
+                st["t"].zero_()
+            torch.cuda.current_stream(self._device).wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._frame(st)
+        # (the capture enqueued nothing: the counter is still 0; every row the warm-up wrote is written again by replay 0)
+        for _ in range(T):
+            graph.replay()
+        st["graph"] = graph  # alive until the caller has synchronised
+
+
+def blink_stability(values, blinks, margin: int = 5) -> np.ndarray:
+    """The reference's blink-stability figure (scripts/evaluate_stability.py:229-245) for one run: `values` [T] or [T, C], one quantity
+    over the frames of a video (hpb, xy or sz); `blinks` (a, b) frame ranges with the eyes closed.  For every blink boundary x - all
+    starts, then all ends - the difference v[x - margin] - v[x + margin]; returns the RMS over the boundaries, [C] (or [1]).  A boundary
+    within `margin` frames of either end of the video is an error, not a silent skip (the reference would wrap around or raise)."""
+    v = np.asarray(values, dtype=np.float64)
+    xs = np.asarray([a for a, _ in blinks] + [b for _, b in blinks], dtype=np.int64)
+    if xs.size == 0:
+        raise ValueError("blink_stability: no blinks given")
+    bad = xs[(xs - margin < 0) | (xs + margin >= len(v))]
+    if bad.size:
+        raise ValueError(f"blink_stability: blink boundaries {bad.tolist()} lie within {margin} frames of the ends of a {len(v)}-frame video")
+    return np.atleast_1d(np.sqrt(np.mean(np.square(v[xs - margin] - v[xs + margin]), axis=0)))
+
 
 class EnsemblePredictor(Predictor):
     """Several networks on ONE crop, averaged on the device (reference: scripts/add_pose_pseudolabels.py:54-127, which runs a `Predictor`
