@@ -138,15 +138,6 @@ ABI_VERSION = 37
 ADAM_HEALTH_SKIPPED, ADAM_HEALTH_CONSECUTIVE, ADAM_HEALTH_CULPRIT, ADAM_HEALTH_WORDS = 0, 1, 2, 4  # TTK_ADAM_HEALTH_*
 
 
-# Whether the backbones hand the running mean to the forward producers as the statistics pivot (include/ttk.h).  Always on in the
-# product; tests/test_bn_pivot_gpu.py and tools flip this attribute for the A/B against plain sums of y and y^2.
-BN_PIVOT = True
-
-
-def bn_pivot() -> bool:
-    return BN_PIVOT
-
-
 MOBILENET_MAX_BLOCKS, MOBILENET_MAX_BUFFERS = 16, 96  # TTK_MOBILENET_MAX_BLOCKS, TTK_MOBILENET_MAX_BUFFERS
 MOBILENET_MODES = {"train": 0, "frozen": 1, "eval": 2}   # TTK_MOBILENET_TRAIN / _FROZEN / _EVAL
 MOBILENET_PRECISIONS = {"fp32": 0, "bf16-compute": 1}    # TTK_MOBILENET_FP32 / _BF16_COMPUTE

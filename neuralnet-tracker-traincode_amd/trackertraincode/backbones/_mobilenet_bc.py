@@ -22,11 +22,6 @@ _BF = 3          # TTK_STORE_ACT_BF16 | TTK_STORE_GRAD_BF16 (stem: C = 32, the s
 _DT = torch.bfloat16
 
 
-# Which weight-gradient folds ride in the launch that finalises a BatchNorm backward (ttk_bc_bn_bwd_finalize_fold) instead of their own launch:
-# 0 none, 1 the depthwise rows, 2 + the slice tiles of the fused early layers, 3 + those of the wide layers (tools/exp/ab_fold_finalize.py)
-_FOLD_WITH_FINALIZE = 2
-
-
 def part_buffer(B, H, W, device, blocks, blur=False):
     """One scratch buffer large enough for every layer's [rows][2][C] partial sums."""
     L = _hip.lib()
@@ -46,14 +41,10 @@ def part_buffer(B, H, W, device, blocks, blur=False):
 
 
 def forward_impl(MB, x, params, buffers, momentum, eps, training, frozen=False, blur=None):
-    """`MB`: the mobilenet_v1 module (block table, `_Stage`, `_Ctx`, `_BnArena`, `_identity_bn`)."""
+    """`MB`: the mobilenet_v1 module (block table, `_Stage`, `_Ctx`, `_BnArena`, `_identity_bn`, the input check and the gradient arena)."""
     L = _hip.lib()
     blocks = MB._BLOCKS
-    blur = list(blur) if blur is not None else [None] * len(blocks)
-    _hip.check_tensors([x], "input")  # (what came from outside is checked once; everything else below is allocated here)
-    _hip.check_tensors(params, "parameter")
-    _hip.check_tensors(buffers, "BatchNorm buffer")
-    _hip.check_tensors(blur, "blur kernel")
+    blur = MB._check_forward_inputs(x, params, buffers, blur, len(blocks))
     p = _hip.fast_ptr
     dev = x.device
     B, _, H, W = x.shape
@@ -64,7 +55,7 @@ def forward_impl(MB, x, params, buffers, momentum, eps, training, frozen=False, 
     ctx.blur = []
     ctx.frozen = frozen
     ctx.stages, ctx.a_in, ctx.dims = [], [], []
-    ctx.bf, ctx.gdt = "bc", _DT
+    ctx.bf16_compute = True
     bns = MB._BnArena([32] + [c for _, cin, cout, _ in blocks for c in (cin, cout)], dev)
 
     def pivot(bi):
@@ -140,17 +131,7 @@ def backward_impl(MB, ctx, gfeat, params):
     p = _hip.fast_ptr
     B, part = ctx.B, ctx.part
     blocks = MB._BLOCKS
-    offs, total = [], 0
-    for q in params:
-        offs.append(total)
-        total += (q.numel() + 63) // 64 * 64
-    offs.append(total)
-    arena = torch.zeros(total, dtype=torch.float32, device=gfeat.device)
-    grads = [arena[o:o + q.numel()].view(q.shape) for o, q in zip(offs, params)]
-
-    def announce(first, last):
-        MB.grad_ready_hook(arena, [(params[i], offs[i], offs[i + 1]) for i in range(first, last)])
-
+    arena, offs, grads = MB._grad_arena(params, gfeat.device, zero=True)
     last = ctx.stages[-1]
     C = last.y.shape[-1]
 
@@ -189,20 +170,22 @@ def backward_impl(MB, ctx, gfeat, params):
         M = B * ho * wo
         # -- pointwise: weight gradient, data gradient (+ bn_dw backward sums)
         g_dw = torch.empty(st_dw.y.shape, dtype=_DT, device=st_dw.y.device)
-        fused_rows = L.cdll.ttk_bc_pw_bwd_fused_rows(M, cin, cout) if MB._FUSED_PW_BWD else 0
-        defer = (not ctx.frozen) and _FOLD_WITH_FINALIZE >= (2 if fused_rows > 0 else 3)  # the slice tiles are folded by the launch that finalises bn_dw's backward
+        fused_rows = L.cdll.ttk_bc_pw_bwd_fused_rows(M, cin, cout)
+        # the fused layers' slice tiles are folded by the launch that finalises bn_dw's backward; those of the wide layers by the weight-gradient
+        # launch itself (every other placement measured slower: profiles/r05_bc_gemm_variants.txt)
+        defer = not ctx.frozen and fused_rows > 0
         dWp = None if defer else p(grads[pi + 3])
         if fused_rows > 0:  # the early layers (HBM-bound): one kernel reads g, y, ydw once for both gradients
             L.call("ttk_bc_pw_bwd_fused", p(g), p(st_pw.y), p(st_pw.bn), p(ctx.prep[k]), p(st_dw.y), p(st_dw.bn), p(g_dw), dWp, p(scratch),
                    p(part), M, cin, cout)
-            rows, slices = fused_rows, fused_rows
+            rows = fused_rows
         else:
             L.call("ttk_bc_pw_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), dWp, p(scratch), M, cin, cout)
             L.call("ttk_bc_pw_bwd_data", p(g), p(st_pw.y), p(st_pw.bn), p(ctx.prep[k]), p(st_dw.y), p(st_dw.bn), p(g_dw), p(part), M, cin, cout)
-            rows, slices = rows_pw(M, cout, cin), L.cdll.ttk_bc_pw_wgrad_slices(M, cin, cout)
+            rows = rows_pw(M, cout, cin)
         if defer:
             L.call("ttk_bc_bn_bwd_finalize_fold", p(part), rows, cin, M, p(params[pi + 1]), p(st_dw.bn), p(grads[pi + 1]), p(grads[pi + 2]), 0,
-                   p(scratch), slices, cin * cout, p(grads[pi + 3]), 1)
+                   p(scratch), fused_rows, cin * cout, p(grads[pi + 3]), 1)
         else:
             bwd_finalize(st_dw, rows, M, pi + 1)
         # -- depthwise: data gradient (+ residual gradient, + producer's bn sums) with the fused weight gradient
@@ -220,23 +203,19 @@ def backward_impl(MB, ctx, gfeat, params):
         else:
             rows = rows_dw(B, h, w_, cin, stride, 1)
             gi = pi - 2 if k > 0 else 1
-            if ctx.frozen or _FOLD_WITH_FINALIZE < 1:
-                L.call("ttk_bc_dw_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), p(g) if has_skip else None, p(st_prev.y), p(st_prev.bn),
-                       p(st_prev.skip), p(a_in), p(g_prev), p(part), p(dWd), 1, dw_scratch, B, h, w_, cin, stride)
+            # frozen: the entry point folds its weight-gradient rows itself (dw_accumulate = 1).  Otherwise it leaves them unfolded (2) and ONE launch
+            # finalises the producer's BatchNorm backward AND folds them (two dependent few-microsecond launches less per layer)
+            L.call("ttk_bc_dw_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), p(g) if has_skip else None, p(st_prev.y), p(st_prev.bn),
+                   p(st_prev.skip), p(a_in), p(g_prev), p(part), p(dWd), 1 if ctx.frozen else 2, dw_scratch, B, h, w_, cin, stride)
+            if ctx.frozen:
                 bwd_finalize(st_prev, rows, B * h * w_, gi)
             else:
-                # the kernel leaves its weight-gradient rows unfolded (dw_accumulate = 2); ONE launch finalises the producer's BatchNorm backward
-                # AND folds them (two dependent few-microsecond launches less per layer)
-                L.call("ttk_bc_dw_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), p(g) if has_skip else None, p(st_prev.y), p(st_prev.bn),
-                       p(st_prev.skip), p(a_in), p(g_prev), p(part), p(dWd), 2, dw_scratch, B, h, w_, cin, stride)
                 L.call("ttk_bc_bn_bwd_finalize_fold", p(part), rows, cin, B * h * w_, p(params[gi]), p(st_prev.bn), p(grads[gi]), p(grads[gi + 1]), 0,
                        dw_scratch, rows, 9 * cin, p(dWd), 1)
         g = g_prev
-        if MB.grad_ready_hook is not None:
-            announce(pi, pi + 6)
+        MB._announce(arena, offs, params, pi, pi + 6)
     st0 = ctx.stages[0]
     _, _, H, W = ctx.x.shape
     L.call("ttk_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 1, stem_scratch, B, H, W, _BF)
-    if MB.grad_ready_hook is not None:
-        announce(0, 3)
+    MB._announce(arena, offs, params, 0, 3)
     return grads

@@ -180,12 +180,10 @@ def get_sequence() -> str:
 def _check_native_product():
     """The native sequence is the PRODUCT configuration of the launch sequences and nothing else: with an experiment switch off its product value
     it refuses instead of silently running something other than what was asked for."""
-    want = (("_ELIDE_HEAD_INPUT", _THIS, ("dw3_1", "dw4_1")), ("_DW_WGRAD_ROWS", _THIS, 2), ("_FUSED_PW_BWD", _THIS, True), ("_USE_WGRAD_STREAM", _THIS, False),
-            ("_EXP_TENSOR_HOOK", _THIS, None), ("_FOLD_WITH_FINALIZE", _mobilenet_bc, 2), ("BN_PIVOT", _hip, True))
-    for name, mod, value in want:
-        have = getattr(mod, name)
+    for name, value in (("_ELIDE_HEAD_INPUT", ("dw3_1", "dw4_1")), ("_EXP_TENSOR_HOOK", None)):
+        have = globals()[name]
         if type(have) is not type(value) or have != value:
-            raise ValueError(f'sequence "native" issues the product launch sequence only: {mod.__name__.rsplit(".", 1)[-1]}.{name} is {have!r}, the product '
+            raise ValueError(f'sequence "native" issues the product launch sequence only: mobilenet_v1.{name} is {have!r}, the product '
                              f'value is {value!r}; use sequence "python" for this experiment')
 
 
@@ -244,7 +242,38 @@ def _part_buffer(B, H, W, device, blur=False, blocks=_BLOCKS, c0=_STEM_CHANNELS)
 
 class _Ctx:
     """Everything one forward pass leaves behind for its backward."""
-    __slots__ = ("x", "stages", "a_in", "part", "dims", "pool_skip", "wparams", "HW", "B", "prep", "bf", "gdt", "frozen", "blur", "blocks")
+    __slots__ = ("x", "stages", "a_in", "part", "dims", "pool_skip", "wparams", "HW", "B", "prep", "bf16_compute", "frozen", "blur", "blocks")
+
+
+_FP32_STORAGE = 0  # the trailing TTK_STORE_* argument of the fp32 entry points: fp32 tensors (the bf16 storage variants under these kernels are retired)
+
+
+def _check_forward_inputs(x, params, buffers, blur, nblocks):
+    """What comes from outside is checked once per forward call (everything else is allocated by the sequence itself) -> `blur` as a list per block."""
+    blur = list(blur) if blur is not None else [None] * nblocks
+    _hip.check_tensors([x], "input")
+    _hip.check_tensors(params, "parameter")
+    _hip.check_tensors(buffers, "BatchNorm buffer")
+    _hip.check_tensors(blur, "blur kernel")
+    return blur
+
+
+def _grad_arena(params, device, zero):
+    """One arena for every parameter gradient, each padded to 64 floats -> (arena, offs, grads): parameter i owns arena[offs[i]:offs[i + 1]],
+    grads[i] is its view in the parameter's shape.  `zero`: the Python sequences' weight-gradient kernels accumulate into it (one fill launch)."""
+    offs, total = [], 0
+    for q in params:
+        offs.append(total)
+        total += (q.numel() + 63) // 64 * 64
+    offs.append(total)
+    arena = (torch.zeros if zero else torch.empty)(total, dtype=torch.float32, device=device)
+    return arena, offs, [arena[o:o + q.numel()].view(q.shape) for o, q in zip(offs, params)]
+
+
+def _announce(arena, offs, params, first, last):
+    """Parameters first .. last-1 are final: their slices of the arena (padding included) may travel - to `grad_ready_hook`, where one is set."""
+    if grad_ready_hook is not None:
+        grad_ready_hook(arena, [(params[i], offs[i], offs[i + 1]) for i in range(first, last)])
 
 
 _IDENTITY_BN: dict = {}
@@ -270,12 +299,8 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
     [Cin,1,3,3] (use_blurpool, strided blocks) or None; `blocks`: the instance's (width-scaled) block table.  Per layer, a shape the
     tuned kernels accept runs on them; every other layer runs on the any-channel-count family (ttk_anyc_*) - same contracts, same layout."""
     L = _hip.lib()
-    blur = list(blur) if blur is not None else [None] * len(blocks)
+    blur = _check_forward_inputs(x, params, buffers, blur, len(blocks))
     c0 = params[0].shape[0]
-    _hip.check_tensors([x], "input")  # what came from outside is checked once; everything else below is allocated here
-    _hip.check_tensors(params, "parameter")
-    _hip.check_tensors(buffers, "BatchNorm buffer")
-    _hip.check_tensors(blur, "blur kernel")
     p = _hip.fast_ptr
     dev = x.device
     B, _, H, W = x.shape
@@ -286,15 +311,13 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
     ctx.blur = []
     ctx.frozen = frozen  # backward through eval-mode BatchNorm: the fixed affine map (ttk_bn_bwd_frozen)
     ctx.stages, ctx.a_in, ctx.dims = [], [], []
-    act_dtype = torch.float32
-    bf = 0  # TTK_STORE_* bits of the C-ABI: fp32 tensors (the bf16 storage variants under these kernels are retired)
-    ctx.bf, ctx.gdt = bf, torch.float32
+    ctx.bf16_compute = False
     bns = _BnArena([c0] + [c for _, cin, cout, _ in blocks for c in (cin, cout)], dev)
 
     def pivot(bi):
         """The statistics pivot of BatchNorm `bi` (include/ttk.h): its running mean - the producer sums y - pivot, the finalisation adds
         it back (and only then updates the running mean)."""
-        return p(buffers[3 * bi]) if _hip.bn_pivot() else None
+        return p(buffers[3 * bi])
 
     def finalize(bn, rows, C, count, gamma, beta, bi):
         rm, rv, nbt = buffers[3 * bi], buffers[3 * bi + 1], buffers[3 * bi + 2]
@@ -308,6 +331,10 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
             # it the pieces are unscaled: values above 65 504 overflow, small activations fall into fp16's subnormal range
             L.call("ttk_bn_frozen_bound", p(part), pivot(bi), rows, C, count, p(bn))
 
+    def exp_hook(k, y):
+        if _EXP_TENSOR_HOOK is not None:
+            _EXP_TENSOR_HOOK("y", k, y)
+
     part_arg = p(part)
     # forward and data-gradient weight operands of all 13 pointwise convs, one launch
     # (the tuned pointwise layers; the any-channel-count GEMMs read the raw weights)
@@ -320,10 +347,10 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
             ctx.prep[k] = t
         L.pwconv_prepare_weights([params[3 + 6 * k + 3] for k in tuned_pw], [ctx.prep[k] for k in tuned_pw])
     # ---- stem (reference :122-126,161-163)
-    y0 = torch.empty((B, Ho, Wo, c0), dtype=act_dtype, device=dev)
+    y0 = torch.empty((B, Ho, Wo, c0), dtype=torch.float32, device=dev)
     bn = bns.take(c0)
     if c0 == _STEM_CHANNELS:
-        L.call("ttk_stem_fwd", p(x), p(params[0]), p(y0), part_arg, pivot(0), B, H, W, bf)
+        L.call("ttk_stem_fwd", p(x), p(params[0]), p(y0), part_arg, pivot(0), B, H, W, _FP32_STORAGE)
         finalize(bn, L.partial_rows_elementwise(B * Ho * Wo * 8), 32, B * Ho * Wo, params[1], params[2], 0)
     else:
         L.call("ttk_anyc_stem_fwd", p(x), p(params[0]), p(y0), part_arg, pivot(0), B, H, W, c0)
@@ -339,7 +366,7 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
             if st.skip_bn is not None:
                 L.call("ttk_dwconv3x3_fwd_rawskip", p(yprev), p(bn_prev), p(skip_prev), p(st.skip_bn), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride)
             else:
-                L.call("ttk_dwconv3x3_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride, bf)
+                L.call("ttk_dwconv3x3_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride, _FP32_STORAGE)
             return L.partial_rows_dwconv(B, hh, ww, C, stride, False)
         L.call("ttk_anyc_dw_fwd", p(yprev), p(bn_prev), p(skip_prev), p(a_out), p(w), p(y), part_arg, pv, B, hh, ww, C, stride)
         return L.anyc_partial_rows(B * ((hh - 1) // stride + 1) * ((ww - 1) // stride + 1))
@@ -355,13 +382,13 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
         # family keeps storing.)
         head = has_skip and prev.skip is None and _tuned_c(cin) and (_ELIDE_HEAD_INPUT is True or (bool(_ELIDE_HEAD_INPUT) and name in _ELIDE_HEAD_INPUT))
         a_in = torch.empty_like(prev.y) if (has_skip and not head) else None
-        ydw = torch.empty((B, ho, wo, cin), dtype=act_dtype, device=dev)
+        ydw = torch.empty((B, ho, wo, cin), dtype=torch.float32, device=dev)
         k = len(ctx.dims)
         if blur[k] is not None:
             # reference :43-55 - BlurPool2D (binomial 3x3, stride 2) then the depthwise conv at stride 1: two launches of the
             # same depthwise kernel; the blurred tensor crosses HBM once with the identity constant block (its partial sums
             # are written to the scratch rows and overwritten by the next launch)
-            t = torch.empty((B, ho, wo, cin), dtype=act_dtype, device=dev)
+            t = torch.empty((B, ho, wo, cin), dtype=torch.float32, device=dev)
             dw_fwd(prev, None, blur[k], t, None, h, w_, cin, stride)
             st_t = _Stage(t, _identity_bn(cin, dev), None)
             dw_rows = dw_fwd(st_t, None, w_dw, ydw, pivot(bi), ho, wo, cin, 1)
@@ -369,20 +396,18 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
         else:
             dw_rows = dw_fwd(prev, a_in, w_dw, ydw, pivot(bi), h, w_, cin, stride)
             ctx.blur.append(None)
-        if _EXP_TENSOR_HOOK is not None:
-            _EXP_TENSOR_HOOK("y", k, ydw)
+        exp_hook(k, ydw)
         bn_dw = bns.take(cin)
         finalize(bn_dw, dw_rows, cin, B * ho * wo, g_dw, b_dw, bi)
-        ypw = torch.empty((B, ho, wo, cout), dtype=act_dtype, device=dev)
+        ypw = torch.empty((B, ho, wo, cout), dtype=torch.float32, device=dev)
         M = B * ho * wo
         if ctx.prep[k] is not None:
-            L.call("ttk_pwconv1x1_fwd", p(ydw), p(bn_dw), None, p(ypw), part_arg, pivot(bi + 1), M, cin, cout, p(ctx.prep[k]), bf)
+            L.call("ttk_pwconv1x1_fwd", p(ydw), p(bn_dw), None, p(ypw), part_arg, pivot(bi + 1), M, cin, cout, p(ctx.prep[k]), _FP32_STORAGE)
             pw_rows = L.partial_rows_gemm(M, cin, cout)
         else:
             L.call("ttk_anyc_pw_fwd", p(ydw), p(bn_dw), p(w_pw), p(ypw), part_arg, pivot(bi + 1), M, cin, cout)
             pw_rows = L.partial_rows_gemm(M)
-        if _EXP_TENSOR_HOOK is not None:
-            _EXP_TENSOR_HOOK("y", k, ypw)
+        exp_hook(k, ypw)
         bn_pw = bns.take(cout)
         finalize(bn_pw, pw_rows, cout, M, g_pw, b_pw, bi + 1)
         bi += 2
@@ -397,7 +422,7 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
     if _tuned_c(C) and prev.skip_bn is not None:
         L.call("ttk_avgpool_fwd_rawskip", p(prev.y), p(prev.bn), p(prev.skip), p(prev.skip_bn), p(feat), B, h * w_, C)
     elif _tuned_c(C):
-        L.call("ttk_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C, bf)
+        L.call("ttk_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C, _FP32_STORAGE)
     else:
         L.call("ttk_anyc_avgpool_fwd", p(prev.y), p(prev.bn), p(prev.skip), p(feat), B, h * w_, C)
     ctx.HW = h * w_
@@ -410,37 +435,21 @@ def _forward_impl(x, params, buffers, momentum, eps, training, frozen=False, blu
 grad_ready_hook = None
 
 
-# Experiment hooks (module attributes that tools/exp scripts flip; the product never reads the environment for them):
-# _USE_WGRAD_STREAM puts the weight-gradient GEMMs on a second stream beside the data-gradient chain.  It was worth 0.3-0.4 ms/step while
-# the kernels left the GPU half empty at their tails; with today's kernels the serial order is 0.3 % faster (same box, alternating runs:
-# 9.94 vs 9.98 ms; round 6, the wide layers only, the fused early layers kept: 69.1-69.6 k against 69.7-70.3 k crops/s, tools/exp/ab_wgrad_stream.py -
-# the finalisation gaps it could fill are smaller than what two kernels that each want every CU cost one another).  _FUSED_PW_BWD = False selects the
-# two-kernel backward of the first pointwise layers.
-_USE_WGRAD_STREAM = False
+# Settled A/Bs of the backward sequence (the losing arms are in the git history):
+#   everything on ONE stream - weight-gradient GEMMs on a second stream measured slower (69.4 k against 70.1 k crops/s);
+#   weight and data gradient of the early pointwise layers in one kernel wherever ttk_pwconv1x1_bwd_fused_rows() > 0 (profiles/pw_bwd_fused_wide.txt);
+#   depthwise weight gradient as workgroup rows folded by the launch that finalises the producer's BatchNorm backward: 68.9 k against 68.4 k (atomics)
+#   and 67.3 k (rows + a fold launch of their own) - profiles/r05_bc_gemm_variants.txt.
+_USE_WGRAD_STREAM = False  # inert: bench.py saves and restores it, nothing reads it
 # TTK_DETERMINISTIC=1: every weight-gradient reduction runs in a fixed order (slices of M stored to scratch and folded
 # by a second kernel instead of fp32 atomics): two runs of a step give bitwise equal gradients.
 _DETERMINISTIC = os.environ.get("TTK_DETERMINISTIC", "0") != "0"
-_FUSED_PW_BWD = True
 # The first block of a chain of residual blocks (dw3_1, dw4_1, dw5_1, dw6) need not store its input: it is relu(bn(y)) of the producer alone, and its
 # consumers can form it on load (the ttk_*_rawskip entry points).  True: none of the four stores it; False: all do (the stored form: the A/B run,
 # tests/test_rawskip_gpu.py); a tuple of block names: those blocks do not.  The product elides the two large ones.  Behind dw5_1 and dw6 the raw form's
 # consumer measured slower than the stored one (the 9 x 9 x 512 forward of dw5_2 54.1 -> 60.1 us, the pool forward 22.7 -> 23.3 us: the stored input was
 # still in the memory-side cache, the raw tensor three launches back is not), so these two keep storing - profiles/head_block_input.txt.
 _ELIDE_HEAD_INPUT = ("dw3_1", "dw4_1")
-# The fused depthwise weight gradient: 0 = float atomics (the product until round 5), 1 = workgroup rows + their own fold launch (slower: 67.3 k against
-# 68.4 k crops/s), 2 = rows folded inside the launch that finalises the producer's BatchNorm backward (ttk_bc_bn_bwd_finalize_fold: 68.9 k, same box,
-# tools/exp/ab_dw_rows_fp32.py) - the product.  Deterministic mode keeps its own scratch and fold order.
-_DW_WGRAD_ROWS = 2
-_SIDE_STREAMS: dict = {}
-
-
-def _side_stream(device):
-    key = (device.type, device.index)
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[key]
-
-
 # Experiment hook of tools/soak.py (None in the product): called as _EXP_TENSOR_HOOK(kind, block, tensor) right after a kernel has produced
 # a gradient ("g": with respect to a conv output before its BatchNorm) or an activation ("y": a raw conv output) of the fp32 path, e.g. to round it
 # to the bf16 grid in place - how much of the bf16-compute path's soak gap each tensor class explains (profiles/r06_soak_rounding_ab.txt).
@@ -452,18 +461,12 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
     _hip.check_tensors([gfeat], "gradient")
     _hip.check_tensors(params, "parameter")
     p = _hip.fast_ptr
-    B, part, bf, blocks = ctx.B, ctx.part, ctx.bf, ctx.blocks
-    # one zeroed arena for every parameter gradient (the weight-gradient kernels accumulate atomically): one fill launch
-    offs, total = [], 0
-    for q in params:
-        offs.append(total)
-        total += (q.numel() + 63) // 64 * 64
-    offs.append(total)
-    arena = torch.zeros(total, dtype=torch.float32, device=gfeat.device)
-    grads = [arena[o:o + q.numel()].view(q.shape) for o, q in zip(offs, params)]
+    B, part, blocks = ctx.B, ctx.part, ctx.blocks
+    arena, offs, grads = _grad_arena(params, gfeat.device, zero=True)
 
-    def announce(first, last):  # parameters first .. last-1 are final: their slice of the arena (padding included) may travel
-        grad_ready_hook(arena, [(params[i], offs[i], offs[i + 1]) for i in range(first, last)])
+    def exp_hook(k, g):
+        if _EXP_TENSOR_HOOK is not None:
+            _EXP_TENSOR_HOOK("g", k, g)
     last = ctx.stages[-1]
     C = last.y.shape[-1]
 
@@ -475,9 +478,8 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
             return
         L.call("ttk_bn_bwd_finalize", p(part), rows, Cc, count, p(params[gi]), p(stage.bn), p(grads[gi]), p(grads[gi + 1]), 0)
 
-    main = torch.cuda.current_stream(gfeat.device)
-    side = _side_stream(gfeat.device) if (_USE_WGRAD_STREAM and not _DETERMINISTIC and all(q is not None for q in ctx.prep)) else None
-    wg_scratch = None
+    # Scratch of the tuned layers' weight gradients; every launch of this backward runs on the one current stream, so each buffer serves one launch after the other.
+    wg_scratch = dw_rows = None
     if _DETERMINISTIC:
         # one scratch buffer for every weight-gradient reduction of this backward (used one after the other on one stream):
         # slices / workgroups store partial results there and a second kernel folds them in a fixed order
@@ -494,12 +496,10 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
     pw_need = max([L.pwconv_wgrad_scratch_bytes(B * d[2] * d[3], d[4], d[5]) for d in ctx.dims if _tuned_c(d[4]) and _tuned_c(d[5])] + [0])
     pw_scratch = wg_scratch if (wg_scratch is not None and wg_scratch.numel() * 4 >= pw_need) else (
         torch.empty(pw_need // 4, dtype=torch.float32, device=gfeat.device) if pw_need else None)
-    keep = []
-    # The fused depthwise weight gradient of the fp32 kernels: workgroup rows (see _DW_WGRAD_ROWS above; deterministic mode: rows + a fixed-order fold of its own).
+    # the fused depthwise weight gradient: workgroup rows, folded by the launch that finalises the producer's BatchNorm backward
     # (the BlurPool blocks and frozen fine-tuning keep float atomics unless deterministic: they pass `wg_scratch`, not these rows)
-    dw_rows = wg_scratch
     rows_layers = [d for d, bl in zip(ctx.dims, ctx.blur) if bl is None and _tuned_c(d[4])]
-    if dw_rows is None and _DW_WGRAD_ROWS and not ctx.frozen and rows_layers:
+    if rows_layers and not _DETERMINISTIC and not ctx.frozen:
         need = max(L.partial_rows_dwconv(B, d[0], d[1], d[4], d[6], True) * 9 * d[4] for d in rows_layers)
         dw_rows = torch.empty(need, dtype=torch.float32, device=gfeat.device)
 
@@ -515,18 +515,17 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
             any_need = max(any_need, L.anyc_wgrad_scratch_bytes("pw", B * d[2] * d[3], d[4], d[5]))
     any_scratch = torch.empty(any_need // 4, dtype=torch.float32, device=gfeat.device) if any_need else None
 
-    g = torch.empty(last.y.shape, dtype=ctx.gdt, device=last.y.device)
+    g = torch.empty(last.y.shape, dtype=torch.float32, device=last.y.device)
     if _tuned_c(C):
         if last.skip_bn is not None:
             L.call("ttk_avgpool_bwd_rawskip", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(last.skip_bn), p(g), p(part), B, ctx.HW, C)
         else:
-            L.call("ttk_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C, bf)
+            L.call("ttk_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C, _FP32_STORAGE)
         bwd_finalize(last, L.partial_rows_elementwise(B * ctx.HW * (C // 4)), B * ctx.HW, len(params) - 2)
     else:
         L.call("ttk_anyc_avgpool_bwd", p(gfeat), p(last.y), p(last.bn), p(last.skip), p(g), p(part), B, ctx.HW, C)
         bwd_finalize(last, L.anyc_partial_rows(B * ctx.HW), B * ctx.HW, len(params) - 2)
-    if _EXP_TENSOR_HOOK is not None:
-        _EXP_TENSOR_HOOK("g", len(blocks), g)
+    exp_hook(len(blocks), g)
 
     def dw_bwd(g_dw, st_dw, w, skip_grad, st_prev, a_in, g_prev, dw, acc, rows, hh, ww, C, stride):
         """One tuned depthwise data-gradient launch into the output of stage `st_prev` (its residual operand stored or raw)."""
@@ -536,7 +535,7 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
         else:
             # (a stored a_in stands for the whole block input: the residual operand, stored or raw, is not read)
             L.call("ttk_dwconv3x3_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w), p(skip_grad), p(st_prev.y), p(st_prev.bn),
-                   p(st_prev.skip if st_prev.skip_bn is None else None), p(a_in), p(g_prev), p(part), p(dw), acc, p(rows), B, hh, ww, C, stride, bf)
+                   p(st_prev.skip if st_prev.skip_bn is None else None), p(a_in), p(g_prev), p(part), p(dw), acc, p(rows), B, hh, ww, C, stride, _FP32_STORAGE)
 
     for k in range(len(blocks) - 1, -1, -1):
         h, w_, ho, wo, cin, cout, stride, has_skip = ctx.dims[k]
@@ -545,57 +544,38 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
         st_prev, st_dw, st_pw = ctx.stages[2 * k], ctx.stages[2 * k + 1], ctx.stages[2 * k + 2]
         a_in = ctx.a_in[k]
         M = B * ho * wo
-        # -- pointwise: weight gradient, then data gradient (+ bn_dw backward sums).  The weight gradient has no
-        # consumer inside backward, so it runs on a second HIP stream next to the data-gradient chain: its
-        # tail (too few tiles left for 256 CUs) and the HBM-bound depthwise kernels fill each other's gaps.
+        # -- pointwise: weight gradient, data gradient (+ bn_dw backward sums)
         dW = grads[pi + 3]
-        g_dw = torch.empty(st_dw.y.shape, dtype=ctx.gdt, device=st_dw.y.device)
+        g_dw = torch.empty(st_dw.y.shape, dtype=torch.float32, device=st_dw.y.device)
         pw_tuned = ctx.prep[k] is not None
-        fused_rows = L.cdll.ttk_pwconv1x1_bwd_fused_rows(M, cin, cout) if (_FUSED_PW_BWD and bf == 0 and pw_tuned) else 0  # (one kernel for both gradients: main stream, with or without the side stream)
+        fused_rows = L.cdll.ttk_pwconv1x1_bwd_fused_rows(M, cin, cout) if pw_tuned else 0
         if not pw_tuned:
             # any-channel-count layer: exact-fp32 MFMA GEMMs from the raw weights; the weight gradient is slice rows + a fixed-order fold
             L.call("ttk_anyc_pw_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), p(dW), 0, p(any_scratch), M, cin, cout)
             L.call("ttk_anyc_pw_bwd_data", p(g), p(st_pw.y), p(st_pw.bn), p(w_pw), p(st_dw.y), p(st_dw.bn), p(g_dw), p(part), M, cin, cout)
             bwd_finalize(st_dw, L.partial_rows_gemm(M), M, pi + 1)
-            if _EXP_TENSOR_HOOK is not None:
-                _EXP_TENSOR_HOOK("g", k, g_dw)
-        elif fused_rows:
+        elif fused_rows > 0:
             # the first five pointwise layers (32 -> 64 .. 256 -> 256: HBM-bound, the largest activations): weight and data gradient in ONE kernel - g,
             # the conv output and the depthwise output are read once instead of twice (csrc/pw_bwd_fused.hip)
             L.call("ttk_pwconv1x1_bwd_fused", p(g), p(st_pw.y), p(st_pw.bn), p(w_pw), p(ctx.prep[k]), p(st_dw.y), p(st_dw.bn), p(g_dw), p(dW),
                    p(wg_scratch), p(part), M, cin, cout)
             bwd_finalize(st_dw, fused_rows, M, pi + 1)
-            if _EXP_TENSOR_HOOK is not None:
-                _EXP_TENSOR_HOOK("g", k, g_dw)
-        elif side is not None:
-            ev = torch.cuda.Event()
-            ev.record(main)  # g, bn_pw backward constants and the zeroed dW are ready
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                L.call("ttk_pwconv1x1_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), p(dW),
-                       p(pw_scratch) if L.pwconv_wgrad_scratch_bytes(M, cin, cout) else None, M, cin, cout, bf)
-                if grad_ready_hook is not None:
-                    done = torch.cuda.Event()
-                    done.record(side)
-            keep.append(g)  # main must not recycle g's memory while the side stream still reads it
         else:
-            L.call("ttk_pwconv1x1_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), p(dW),
-                   p(wg_scratch) if wg_scratch is not None else (p(pw_scratch) if L.pwconv_wgrad_scratch_bytes(M, cin, cout) else None), M, cin, cout, bf)
-        if pw_tuned and not fused_rows:
+            partial = wg_scratch if _DETERMINISTIC else (pw_scratch if L.pwconv_wgrad_scratch_bytes(M, cin, cout) else None)
+            L.call("ttk_pwconv1x1_bwd_weight", p(g), p(st_pw.y), p(st_pw.bn), p(st_dw.y), p(st_dw.bn), p(dW), p(partial), M, cin, cout, _FP32_STORAGE)
             L.call("ttk_pwconv1x1_bwd_data", p(g), p(st_pw.y), p(st_pw.bn), None, p(st_dw.y), p(st_dw.bn), p(g_dw), p(part), M,
-                   cin, cout, p(ctx.prep[k]), bf)
+                   cin, cout, p(ctx.prep[k]), _FP32_STORAGE)
             bwd_finalize(st_dw, L.partial_rows_gemm(M, cout, cin, True), M, pi + 1)
-            if _EXP_TENSOR_HOOK is not None:
-                _EXP_TENSOR_HOOK("g", k, g_dw)
-        # -- depthwise: weight gradient, then data gradient (+ residual gradient, + producer's bn sums)
-        dWd = grads[pi]  # accumulated by the fused weight-gradient path of bwd_data
-        g_prev = torch.empty(st_prev.y.shape, dtype=ctx.gdt, device=st_prev.y.device)
+        exp_hook(k, g_dw)
+        # -- depthwise: data gradient (+ residual gradient, + producer's bn sums) with the fused weight gradient
+        dWd = grads[pi]
+        g_prev = torch.empty(st_prev.y.shape, dtype=torch.float32, device=st_prev.y.device)
         gi_prev = pi - 2 if k > 0 else 1
         if not _tuned_c(cin):
             # any-channel-count layer (BlurPool blocks: the same two steps as below)
             if ctx.blur[k] is not None:
                 st_t, w_blur = ctx.blur[k]
-                g_t = torch.empty(st_t.y.shape, dtype=ctx.gdt, device=st_t.y.device)
+                g_t = torch.empty(st_t.y.shape, dtype=torch.float32, device=st_t.y.device)
                 L.call("ttk_anyc_dw_bwd_data", p(g_dw), p(st_dw.y), p(st_dw.bn), p(w_dw), None, p(st_t.y), p(st_t.bn), None, None, p(g_t),
                        p(part), p(dWd), 0, p(any_scratch), B, ho, wo, cin, 1)
                 L.call("ttk_bn_bwd_frozen", p(st_t.bn), cin)
@@ -610,38 +590,29 @@ def _backward_impl(ctx: _Ctx, gfeat, params):
             # the mask [t > 0] only drops gradient that the producer's own mask drops as well - t = 0 means every tap was 0), then
             # through the fixed blur kernel (no weight gradient) to the block input
             st_t, w_blur = ctx.blur[k]
-            g_t = torch.empty(st_t.y.shape, dtype=ctx.gdt, device=st_t.y.device)
+            g_t = torch.empty(st_t.y.shape, dtype=torch.float32, device=st_t.y.device)
             dw_bwd(g_dw, st_dw, w_dw, None, st_t, None, g_t, dWd, 1, wg_scratch, ho, wo, cin, 1)  # (float atomics unless deterministic: rows + an own fold launch measured slower)
             L.call("ttk_bn_bwd_frozen", p(st_t.bn), cin)
             dw_bwd(g_t, st_t, w_blur, None, st_prev, None, g_prev, None, 0, None, h, w_, cin, stride)
-            bwd_finalize(st_prev, L.partial_rows_dwconv(B, h, w_, cin, stride, True), B * h * w_, pi - 2 if k > 0 else 1)
-        elif _DW_WGRAD_ROWS == 2 and not _DETERMINISTIC and not ctx.frozen:
-            # workgroup rows, folded by the launch that finalises the producer's BatchNorm backward (one launch instead of atomics + nothing / rows + fold)
-            rows, gi = L.partial_rows_dwconv(B, h, w_, cin, stride, True), (pi - 2 if k > 0 else 1)
+            bwd_finalize(st_prev, L.partial_rows_dwconv(B, h, w_, cin, stride, True), B * h * w_, gi_prev)
+        elif not _DETERMINISTIC and not ctx.frozen:
+            # workgroup rows, folded by the launch that finalises the producer's BatchNorm backward
+            rows = L.partial_rows_dwconv(B, h, w_, cin, stride, True)
             dw_bwd(g_dw, st_dw, w_dw, g if has_skip else None, st_prev, a_in, g_prev, dWd, 2, dw_rows, h, w_, cin, stride)
-            L.call("ttk_bc_bn_bwd_finalize_fold", p(part), rows, cin, B * h * w_, p(params[gi]), p(st_prev.bn), p(grads[gi]), p(grads[gi + 1]), 0,
+            L.call("ttk_bc_bn_bwd_finalize_fold", p(part), rows, cin, B * h * w_, p(params[gi_prev]), p(st_prev.bn), p(grads[gi_prev]), p(grads[gi_prev + 1]), 0,
                    p(dw_rows), rows, 9 * cin, p(dWd), 1)
         else:
-            dw_bwd(g_dw, st_dw, w_dw, g if has_skip else None, st_prev, a_in, g_prev, dWd, 1,
-                   dw_rows if (_DW_WGRAD_ROWS == 1 and not ctx.frozen) else wg_scratch, h, w_, cin, stride)  # (_DW_WGRAD_ROWS = 1: the A/B form, rows + own fold)
-            bwd_finalize(st_prev, L.partial_rows_dwconv(B, h, w_, cin, stride, True), B * h * w_, pi - 2 if k > 0 else 1)
+            dw_bwd(g_dw, st_dw, w_dw, g if has_skip else None, st_prev, a_in, g_prev, dWd, 1, wg_scratch, h, w_, cin, stride)
+            bwd_finalize(st_prev, L.partial_rows_dwconv(B, h, w_, cin, stride, True), B * h * w_, gi_prev)
         g = g_prev
-        if _EXP_TENSOR_HOOK is not None:
-            _EXP_TENSOR_HOOK("g", k, g)
-        if grad_ready_hook is not None:  # this block's conv + bn_dw gradients and its own bn_sep gradients are final
-            if side is not None:
-                main.wait_event(done)
-            announce(pi, pi + 6)
+        exp_hook(k, g)
+        _announce(arena, offs, params, pi, pi + 6)  # this block's conv + bn_dw gradients and its own bn_sep gradients are final
     st0 = ctx.stages[0]
     if c0 == _STEM_CHANNELS:
-        L.call("ttk_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 1, p(wg_scratch), B, H, W, bf)
+        L.call("ttk_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 1, p(wg_scratch), B, H, W, _FP32_STORAGE)
     else:
         L.call("ttk_anyc_stem_bwd_weight", p(g), p(st0.y), p(st0.bn), p(ctx.x), p(grads[0]), 0, p(any_scratch), B, H, W, c0)
-    if grad_ready_hook is not None:
-        announce(0, 3)
-    if side is not None:
-        main.wait_stream(side)  # join: everything after backward (clip+Adam) sees the weight gradients
-        keep.clear()
+    _announce(arena, offs, params, 0, 3)
     return grads
 
 
@@ -658,13 +629,9 @@ def _native_forward(x, params, buffers, momentum, eps, mode, blur, precision, bl
     """ttk_mobilenet_forward: the launches of _forward_impl / _mobilenet_bc.forward_impl as one C call.  `mode`: "train" | "frozen" | "eval"."""
     _check_native_product()
     L = _hip.lib()
-    blur = list(blur) if blur is not None else [None] * len(blocks)
-    _hip.check_tensors([x], "input")
-    _hip.check_tensors(params, "parameter")
-    _hip.check_tensors(buffers, "BatchNorm buffer")
-    _hip.check_tensors(blur, "blur kernel")
+    blur = _check_forward_inputs(x, params, buffers, blur, len(blocks))
     B, _, H, W = x.shape
-    plan = L.mobilenet_plan(B, H, W, params[0].shape[0], tuple((cin, cout, stride) for _, cin, cout, stride in blocks), tuple(b is not None for b in blur),
+    plan =L.mobilenet_plan(B, H, W, params[0].shape[0], tuple((cin, cout, stride) for _, cin, cout, stride in blocks), tuple(b is not None for b in blur),
                             mode, precision, _DETERMINISTIC)
     c = _NativeCtx()
     c.plan, c.x, c.blur = plan, x, blur  # (blur: the tensors behind blur_arr stay alive)
@@ -681,23 +648,16 @@ def _native_backward(c: _NativeCtx, gfeat, params):
     _hip.check_tensors([gfeat], "gradient")
     _hip.check_tensors(params, "parameter")
     plan = c.plan
-    offs, total = [], 0
-    for q in params:
-        offs.append(total)
-        total += (q.numel() + 63) // 64 * 64
-    offs.append(total)
-    if total != plan.arena_floats or len(params) != plan.nparams:
-        raise RuntimeError(f"native backward: the parameters take {total} arena floats in {len(params)} tensors, the plan {plan.arena_floats} in {plan.nparams}")
-    arena = torch.empty(total, dtype=torch.float32, device=gfeat.device)  # (zeroed by the C side on this stream)
-    grads = [arena[o:o + q.numel()].view(q.shape) for o, q in zip(offs, params)]
+    arena, offs, grads = _grad_arena(params, gfeat.device, zero=False)  # (zeroed by the C side on this stream)
+    if offs[-1] != plan.arena_floats or len(params) != plan.nparams:
+        raise RuntimeError(f"native backward: the parameters take {offs[-1]} arena floats in {len(params)} tensors, the plan {plan.arena_floats} in {plan.nparams}")
     bws = torch.empty(plan.ws_bytes[1], dtype=torch.uint8, device=gfeat.device)
     cb, failed = None, []
-    hook = grad_ready_hook
-    if hook is not None:
+    if grad_ready_hook is not None:
         def ready(_user, first, last):  # (an exception must not unwind through the C frames: kept, raised after the call)
             if not failed:
                 try:
-                    hook(arena, [(params[i], offs[i], offs[i + 1]) for i in range(first, last)])
+                    _announce(arena, offs, params, first, last)
                 except BaseException as e:  # noqa: BLE001
                     failed.append(e)
         cb = _hip.MOBILENET_READY_FN(ready)
@@ -728,7 +688,7 @@ class _MobileNetFn(torch.autograd.Function):
         params = ctx.saved_tensors
         if isinstance(ctx.c, _NativeCtx):
             grads = _native_backward(ctx.c, gfeat.contiguous(), params)
-        elif ctx.c.bf == "bc":
+        elif ctx.c.bf16_compute:
             grads = _mobilenet_bc.backward_impl(_THIS, ctx.c, gfeat.contiguous(), params)
         else:
             grads = _backward_impl(ctx.c, gfeat.contiguous(), params)

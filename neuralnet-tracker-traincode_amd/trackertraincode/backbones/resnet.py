@@ -115,7 +115,7 @@ def _forward_impl(x, params, buffers, momentum, eps, training=True, blur=False):
 
     def pivot():
         """Statistics pivot (include/ttk.h) of the BatchNorm the NEXT finalize() call handles: its running mean, before the update."""
-        return p(buffers[3 * bi[0]]) if (training and _hip.bn_pivot()) else None
+        return p(buffers[3 * bi[0]]) if training else None
 
     def finalize(bn, rows, C, count, gamma, beta, scratch=None):
         rm, rv, nbt = buffers[3 * bi[0]: 3 * bi[0] + 3]
