@@ -11,41 +11,13 @@
 
 #include "bc_common.h"
 
-// Timing-only bits of the backward kernel (experiment builds: tools/exp/build_variants.sh ... "-DTTK_BC_DBG=<bits>"; wrong results):
-//   1 no tap arithmetic (G and the weight-gradient accumulators)   2 no tap LDS reads   4 no store of g_prev
-//   8 no statistics                                                 16 no second-phase global loads
-//   32 no second phase at all                                       64 no staging phase (loads, BatchNorm-backward map, LDS stores)
-//   256 tap operands not widened (forward and backward)
-//   128 no weight-gradient accumulation (72 registers less: occupancy probes with TTK_BC_BLOCK / TTK_BC_WPE)
-#ifndef TTK_BC_DBG
-#define TTK_BC_DBG 0
-#endif
-#ifndef TTK_BC_STAGGER
-#define TTK_BC_STAGGER 0
-#endif
-// threads per workgroup / workgroups per CU of the backward kernel (experiment builds: occupancy probes; the product is 256 x 2)
-#ifndef TTK_BC_BLOCK
-#define TTK_BC_BLOCK 256
-#endif
-#ifndef TTK_BC_WPE
-#define TTK_BC_WPE 2
-#endif
-// ring depths of the backward kernel (experiment builds may override them)
-#ifndef TTK_BC_RING_STAGE
-#define TTK_BC_RING_STAGE 4
-#endif
-#ifndef TTK_BC_RING_LEAN
-#define TTK_BC_RING_LEAN 6
-#endif
-#ifndef TTK_BC_RING_FULL
-#define TTK_BC_RING_FULL 2
-#endif
-
 namespace ttk {
 namespace bc {
 
-constexpr int kBlock = TTK_BC_BLOCK;  // (shadows ttk::kBlock inside this namespace)
 constexpr int kWvs = kBlock / kWave;
+constexpr int kWpe = 2;  // waves per SIMD of both kernels = workgroups of kBlock threads per CU (kWgsFwd, kWgsBwd)
+// load-ring depths of the backward kernel: staging of dy | second phase without / with residual operands (1 / 3 tensors per pixel)
+constexpr int kRingStage = 4, kRingLean = 6, kRingFull = 2;
 
 constexpr int kPixBudgetFwd = 560;  // 128-byte pixels per LDS stage: 70 KB -> 2 workgroups per CU (three, with 168 registers, spilled around the load ring)
 constexpr int kPixBudgetBwd = 512;  // 64 KB + 13 KB of taps / reduction scratch / constants: TWO workgroups per CU fit the 160 KB (560 did not: one per CU, one wave per SIMD); 72 weight-gradient accumulators per lane: <= 256 registers
@@ -109,15 +81,6 @@ struct TileDiv {  // exact n / d for the tile-local indices (dwconv_tiled.hip)
   __device__ __forceinline__ unsigned div(unsigned n) const { return (unsigned)(((float)n + 0.5f) * inv); }
 };
 
-// timing-only (TTK_BC_DBG & 256): the tap operands are NOT widened (what an fp32 LDS tile would save in the tap loops; wrong results)
-__device__ __forceinline__ void unpack_tap(uint4 u, f2 (&v)[4]) {
-  if (TTK_BC_DBG & 256) {
-    v[0] = f2{__uint_as_float(u.x), __uint_as_float(u.y)}; v[1] = f2{__uint_as_float(u.z), __uint_as_float(u.w)};
-    v[2] = f2{__uint_as_float(u.x), __uint_as_float(u.z)}; v[3] = f2{__uint_as_float(u.y), __uint_as_float(u.w)};
-  } else {
-    unpack_f2(u, v);
-  }
-}
 // per-channel sums of the workgroup -> part_row[0][c], part_row[1][c] (fixed wave order); lanes KQ apart own the same chunk
 template <int SL>
 __device__ __forceinline__ void slab_partials(f2 (&s1)[4], f2 (&s2)[4], int q, int C, int c_slab, float* part_row, float* red /* [4][2][SL] */) {
@@ -160,7 +123,7 @@ __device__ __forceinline__ void stage_taps(float* wt, const float* __restrict__ 
 // forward
 // ---------------------------------------------------------------------------------------------
 template <int S, bool SKIP, int SL, bool CARRY>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_BC_WPE, TTK_BC_WPE)))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWpe, kWpe)))
 bc_dw_fwd_k(const bf16_t* __restrict__ yprev, const float* __restrict__ bn_prev, const bf16_t* __restrict__ skip_prev, bf16_t* __restrict__ a_out,
             const float* __restrict__ w, bf16_t* __restrict__ y, float* __restrict__ part, const float* __restrict__ pivot, int B, int H, int W, int C,
             int Ho, int Wo, int R, int nbands, int nslabs, int NI_, int NCT_, int TW, int stage_pix) {
@@ -197,8 +160,6 @@ bc_dw_fwd_k(const bf16_t* __restrict__ yprev, const float* __restrict__ bn_prev,
   int prev_img = -1, prev_band = -2, prev_nrows = 0;
   constexpr int OV = 3 - S;
   __syncthreads();  // taps staged
-  if (TTK_BC_STAGGER && blockIdx.x >= gridDim.x / 2 && tiles >= 4u * wgs)
-    for (int i = 0; i < TTK_BC_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
   for (unsigned t = t_begin; t < t_end; t += t_step) {
     const unsigned tb = t / (unsigned)NCT, ti = tb / (unsigned)nbands;
     const int ct = (int)(t - tb * NCT), band = (int)(tb - ti * nbands), n0 = (int)ti * NI;
@@ -310,7 +271,7 @@ bc_dw_fwd_k(const bf16_t* __restrict__ yprev, const float* __restrict__ bn_prev,
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
           f2 a[4], wv[4];
-          unpack_tap(base[(kh * Wp + kw) * KQ], a);
+          unpack_f2(base[(kh * Wp + kw) * KQ], a);
           ld8(wt + (kh * 3 + kw) * SL + 8 * q, wv);
 #pragma unroll
           for (int k = 0; k < 4; ++k) acc[k] = fma2(a[k], wv[k], acc[k]);
@@ -334,7 +295,7 @@ bc_dw_fwd_k(const bf16_t* __restrict__ yprev, const float* __restrict__ bn_prev,
 // data gradient (+ fused weight gradient)
 // ---------------------------------------------------------------------------------------------
 template <int S, int SL, bool LEAN>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_BC_WPE, TTK_BC_WPE)))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWpe, kWpe)))
 bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, const float* __restrict__ bn_dw, const float* __restrict__ w,
             const bf16_t* __restrict__ skip_grad, const bf16_t* __restrict__ yprev, const float* __restrict__ bn_prev, const bf16_t* __restrict__ skip_prev,
             const bf16_t* __restrict__ a_in, bf16_t* __restrict__ g_prev, float* __restrict__ part, float* __restrict__ dwgrad, float* __restrict__ dw_partial,
@@ -369,8 +330,6 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
 #pragma unroll
     for (int k = 0; k < 4; ++k) wacc[t][k] = f2{0.f, 0.f};
   const unsigned tiles = (unsigned)((B + NI - 1) / NI) * nbands * NCT;
-  if (TTK_BC_STAGGER && blockIdx.x >= gridDim.x / 2 && tiles >= 4u * (gridDim.x / nslabs))
-    for (int i = 0; i < TTK_BC_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
   for (unsigned t = blockIdx.x / nslabs; t < tiles; t += gridDim.x / nslabs) {
     const unsigned tb = t / (unsigned)NCT, ti = tb / (unsigned)nbands;
     const int ct = (int)(t - tb * NCT), band = (int)(tb - ti * nbands), n0 = (int)ti * NI;
@@ -398,7 +357,7 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
     // issued unconditionally - clamped address - so that the counted vmcnt waits stay exact).
     const int nstage = nimg * (int)PI * KQ;
     {
-      constexpr int U = 1, RING = TTK_BC_RING_STAGE;  // 2 x RING 16-byte loads in flight per thread
+      constexpr int U = 1, RING = kRingStage;  // 2 x RING 16-byte loads in flight per thread
       f2 ga[4], gb[4], gc[4];
       ld8(cst + 3 * SL + 8 * q, ga);
       ld8(cst + 4 * SL + 8 * q, gb);
@@ -436,15 +395,13 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
         }
       };
       Stg ring[RING];
-      if (!(TTK_BC_DBG & 64)) {
 #pragma unroll
-        for (int j = 0; j < RING; ++j) issue(tid + j * kBlock, ring[j]);
-        for (int e = tid; e < nstage; e += RING * kBlock) {
+      for (int j = 0; j < RING; ++j) issue(tid + j * kBlock, ring[j]);
+      for (int e = tid; e < nstage; e += RING * kBlock) {
 #pragma unroll
-          for (int j = 0; j < RING; ++j) {
-            finish(e + j * kBlock, ring[j]);
-            issue(e + (j + RING) * kBlock, ring[j]);
-          }
+        for (int j = 0; j < RING; ++j) {
+          finish(e + j * kBlock, ring[j]);
+          issue(e + (j + RING) * kBlock, ring[j]);
         }
       }
     }
@@ -485,7 +442,6 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
           constexpr int kh0 = S == 1 ? 0 : (PH + 1) & 1, kw0 = S == 1 ? 0 : (PW + 1) & 1;
           I.lb = (int)__umul24(img, PI) + __mul24((hi + 1 - kh0) / S - ho_lo, Wp) + (wi + 1 - kw0) / S - cx0 + 1;
         }
-        if (TTK_BC_DBG & 16) { I.yp = u32x4{(unsigned)off, 1u, 2u, 3u}; I.raw = I.yp; I.sg = I.yp; return; }
         I.yp = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(yptile + off));
         if (!LEAN) {
           if (a_in) I.raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(aitile + off));
@@ -535,7 +491,7 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
             // (stride 2: the taps of the class; stride 1: rows -1 .. H, columns -1 .. W - the zero border of the stage)
             constexpr int kh0 = S == 1 ? 0 : (PH + 1) & 1, kw0 = S == 1 ? 0 : (PW + 1) & 1;
             const int idx = lb - __mul24((kh - kh0) / S, Wp) - (kw - kw0) / S;
-            dv[kh * 3 + kw] = (TTK_BC_DBG & 2) ? make_uint4(idx, off, kh, kw) : dyimg[idx << kQs];
+            dv[kh * 3 + kw] = dyimg[idx << kQs];
           }
         f2 G[4];
 #pragma unroll
@@ -543,14 +499,13 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
           if (S == 2 && (((PH + 1 - t / 3) & 1) || ((PW + 1 - t % 3) & 1))) continue;
-          if (TTK_BC_DBG & 1) { G[0].x += __uint_as_float(dv[t].x ^ dv[t].y ^ dv[t].z ^ dv[t].w); continue; }
           f2 dy[4], wv[4];
-          unpack_tap(dv[t], dy);
+          unpack_f2(dv[t], dy);
           ld8(wt + t * SL + 8 * q, wv);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             G[k] = fma2(dy[k], wv[k], G[k]);
-            if (!(TTK_BC_DBG & 128)) wacc[t][k] = fma2(dy[k], a[k], wacc[t][k]);
+            wacc[t][k] = fma2(dy[k], a[k], wacc[t][k]);
           }
         }
         if (!LEAN && skip_grad) {
@@ -565,11 +520,9 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
           G[k].y = a[k].y > 0.f ? G[k].y : 0.f;
         }
         const uint4 o = pack_f2(G);
-        if (!(TTK_BC_DBG & 4)) st16(gptile + off, o);
-        else if (o.x == 0x12345u) st16(gptile + off, o);
+        st16(gptile + off, o);
         f2 gp[4];
         unpack_f2(o, gp);  // sums of what is stored
-        if (TTK_BC_DBG & 8) { s1[0] += gp[0] + gp[1] + gp[2] + gp[3]; return; }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           s1[k] += gp[k];
@@ -577,7 +530,7 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
         }
       };
       // a ring of items: one is processed, its slot refilled at once - RING pixels' loads (1 or 3 tensors each) in flight per thread
-      constexpr int RING = LEAN ? TTK_BC_RING_LEAN : TTK_BC_RING_FULL;
+      constexpr int RING = LEAN ? kRingLean : kRingFull;
       const int nit = (npix + kPixSlots - 1) / kPixSlots;
       Item ring[RING];
 #pragma unroll
@@ -593,7 +546,6 @@ bc_dw_bwd_k(const bf16_t* __restrict__ g_dw, const bf16_t* __restrict__ y_dw, co
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using IA = std::integral_constant<int, -1>;
-    if (TTK_BC_DBG & 32) continue;
     if constexpr (S == 1) {
       run(IA{}, IA{});
     } else {
@@ -665,7 +617,7 @@ int ttk_bc_dw_fwd(const void* yprev, const float* bn_prev, const void* skip_prev
   const size_t sm = (size_t)stage_pix * t.SL * 2 + (size_t)(9 + 2 * kWvs) * t.SL * sizeof(float);
 #define TTK_BC_FWD3(S_, SK_, SL_, CY_)                                                                                                            \
   (void)allow_big_lds<bc_dw_fwd_k<S_, SK_, SL_, CY_>>();                                                                                                \
-  hipLaunchKernelGGL((bc_dw_fwd_k<S_, SK_, SL_, CY_>), dim3(t.grid), dim3(bc::kBlock), sm, (hipStream_t)stream, (const bf16_t*)yprev, bn_prev,          \
+  hipLaunchKernelGGL((bc_dw_fwd_k<S_, SK_, SL_, CY_>), dim3(t.grid), dim3(kBlock), sm, (hipStream_t)stream, (const bf16_t*)yprev, bn_prev,          \
                      (const bf16_t*)skip_prev, (bf16_t*)a_out, w, (bf16_t*)y, part, pivot, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, t.NI, t.NCT, t.TW, stage_pix)
 #define TTK_BC_FWD2(S_, SK_, SL_) do { if (t.carry) { TTK_BC_FWD3(S_, SK_, SL_, true); } else { TTK_BC_FWD3(S_, SK_, SL_, false); } } while (0)
 #define TTK_BC_FWD1(S_, SK_) do { if (t.SL == 64) TTK_BC_FWD2(S_, SK_, 64); else TTK_BC_FWD2(S_, SK_, 32); } while (0)
@@ -695,7 +647,7 @@ int ttk_bc_dw_bwd_data(const void* g_dw, const void* y_dw, const float* bn_dw, c
 #define TTK_BC_BWD3(S_, SL_, LEAN_)                                                                                                               \
   do {                                                                                                                                            \
     (void)allow_big_lds<bc_dw_bwd_k<S_, SL_, LEAN_>>();                                                                                                \
-    hipLaunchKernelGGL((bc_dw_bwd_k<S_, SL_, LEAN_>), dim3(t.grid), dim3(bc::kBlock), sm, st, (const bf16_t*)g_dw, (const bf16_t*)y_dw, bn_dw, w,      \
+    hipLaunchKernelGGL((bc_dw_bwd_k<S_, SL_, LEAN_>), dim3(t.grid), dim3(kBlock), sm, st, (const bf16_t*)g_dw, (const bf16_t*)y_dw, bn_dw, w,      \
                        (const bf16_t*)skip_grad, (const bf16_t*)yprev, bn_prev, (const bf16_t*)skip_prev, (const bf16_t*)a_in, (bf16_t*)g_prev, part, dw, \
                        dw_partial, B, H, W, C, Ho, Wo, t.R, t.nbands, t.nslabs, stage_pix, t.NI, t.NCT, t.TW);                                     \
   } while (0)

@@ -18,12 +18,6 @@
 //                two-slot LDS ring (plain loads one step ahead + ds_write), one barrier per step.
 #include "bc_common.h"
 
-// Timing-only bits of bc_gemm_l_k's main loop (experiment builds: tools/exp/build_variants.sh ... "-DTTK_BC_GDBG=<bits>"; wrong results):
-//   1 no MFMAs   2 no global loads   4 no operand staging (BatchNorm map + LDS stores)   8 no fragment reads   16 no epilogue (mask loads, stores, sums)
-#ifndef TTK_BC_GDBG
-#define TTK_BC_GDBG 0
-#endif
-
 namespace ttk {
 namespace bc {
 
@@ -318,21 +312,18 @@ __global__ void __launch_bounds__(512) bc_gemm_l_k(const bf16_t* __restrict__ A0
     for (int s4 = 0; s4 < 4; ++s4) {
       uint4 av[2], wv[NBW];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) av[j] = (TTK_BC_GDBG & 8) ? make_uint4(kb, s4, j, lane) : As[arow + 256 * j + ((2 * s4 + h) ^ asw)];
+      for (int j = 0; j < 2; ++j) av[j] = As[arow + 256 * j + ((2 * s4 + h) ^ asw)];
 #pragma unroll
-      for (int nb = 0; nb < NBW; ++nb) wv[nb] = (TTK_BC_GDBG & 8) ? make_uint4(kb, s4, nb, lane) : Ws[wrow + 256 * nb + ((2 * s4 + h) ^ wsw)];
+      for (int nb = 0; nb < NBW; ++nb) wv[nb] = Ws[wrow + 256 * nb + ((2 * s4 + h) ^ wsw)];
 #pragma unroll
       for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (TTK_BC_GDBG & 1) { acc[j][nb][0] += __uint_as_float(wv[nb].x ^ av[j].y ^ wv[nb].z ^ av[j].w); continue; }
+        for (int j = 0; j < 2; ++j)
           acc[j][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wv[nb]), __builtin_bit_cast(bf16x8, av[j]), acc[j][nb], 0, 0, 0);
-        }
       // behind them (the matrix pipe leaves three quarters of the issue slots to vector instructions): chunk s4 of the next step into the
       // other slot (last read a step ago: every wave has passed a barrier since), and its registers refilled for the step after
-      if (!(TTK_BC_GDBG & 4)) store_chunk(slot ^ 1, knext, s4);
-      else acc[0][0][1] += __uint_as_float(rx0[s4].x ^ wr[s4].y);
-      if (!(TTK_BC_GDBG & 2)) load_chunk(knn, s4);
+      store_chunk(slot ^ 1, knext, s4);
+      load_chunk(knn, s4);
     }
     __syncthreads();
   }
@@ -342,7 +333,7 @@ __global__ void __launch_bounds__(512) bc_gemm_l_k(const bf16_t* __restrict__ A0
   const int o8 = lane & 7;
   uint4 mk[2][4];
   auto load_mask = [&](int q4, uint4(&d)[4]) {  // q4 = 2 * (local channel block) + pixel group
-    if constexpr (MODE == kDgrad && !(TTK_BC_GDBG & 16)) {
+    if constexpr (MODE == kDgrad) {
       const int cb = n0 / 64 + NCB * wc + (q4 >> 1);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -364,7 +355,6 @@ __global__ void __launch_bounds__(512) bc_gemm_l_k(const bf16_t* __restrict__ A0
       const int q4 = 2 * cbl + j;
       if (q4 + 1 < 2 * NCB) load_mask(q4 + 1, mk[(q4 + 1) & 1]);
       const int64_t g0 = p0 + 64 * wp + 32 * j;
-      if ((TTK_BC_GDBG & 16) && acc[j][2 * cbl][0] != 12345.f) continue;  // (timing only: no epilogue)
       if (g0 < pend)
         store_block<MODE, 64>(acc[j] + 2 * cbl, mystg, out + ((size_t)cb * M + g0) * 64, mk[q4 & 1], cE + 64 * (NCB * wc + cbl), NCT, g0, pend, s1, s2);
     }

@@ -10,12 +10,6 @@
 // of float atomics on one tile would cost more than the plain stores and the fold).
 #include "bc_common.h"
 
-// Timing-only bits (experiment builds: tools/exp/build_variants.sh ... "-DTTK_BC_WDBG=<bits>"; wrong results):
-//   1 no MFMAs   2 no global loads   4 no staging (BatchNorm maps + LDS stores)   8 no fragment reads   16 no tile stores
-#ifndef TTK_BC_WDBG
-#define TTK_BC_WDBG 0
-#endif
-
 namespace ttk {
 namespace bc {
 
@@ -74,13 +68,7 @@ __global__ void __launch_bounds__(512) bc_wgrad_k(const bf16_t* __restrict__ G, 
   const bf16_t* Xb = X + (size_t)(ck / wi) * M * wi + (ck % wi) + (size_t)m_begin * wi;
   u32x4 rg[IN], ry[IN], rx[IK];
   auto load = [&](int c) {
-    if (TTK_BC_WDBG & 2) {
-#pragma unroll
-      for (int i = 0; i < IN; ++i) rg[i] = ry[i] = u32x4{(unsigned)c, (unsigned)i, (unsigned)tid, 1u};
-#pragma unroll
-      for (int i = 0; i < IK; ++i) rx[i] = u32x4{(unsigned)c, (unsigned)i, (unsigned)tid, 2u};
-      return;
-    }
+    (void)tid;  // (named so that the closure keeps the layout it had with the timing legs: without it hipcc orders two scalar instructions of two forms differently)
 #pragma unroll
     for (int i = 0; i < IN; ++i) {
       const unsigned rel = (unsigned)min(c * CP + i * PXN + pn0, nrel - 1);
@@ -94,10 +82,6 @@ __global__ void __launch_bounds__(512) bc_wgrad_k(const bf16_t* __restrict__ G, 
     }
   };
   auto store_to = [&](int c, int slot) {
-    if (TTK_BC_WDBG & 4) {
-      asm volatile("" ::"v"(rg[0].x), "v"(ry[0].x), "v"(rx[0].x));
-      return;
-    }
     unsigned char* buf = lds + slot * kBuf;
     const uint4 zero = make_uint4(0, 0, 0, 0);
 #pragma unroll
@@ -149,16 +133,13 @@ __global__ void __launch_bounds__(512) bc_wgrad_k(const bf16_t* __restrict__ G, 
         if (ks % KS != wsub) continue;
         bf16x8 a[BN], b[BK];
 #pragma unroll
-        for (int i = 0; i < BN; ++i) a[i] = (TTK_BC_WDBG & 8) ? __builtin_bit_cast(bf16x8, make_uint4(c, ks, i, lane)) : tr_frag(buf, aoff[i] + ks * 16 * PN, PN);
+        for (int i = 0; i < BN; ++i) a[i] = tr_frag(buf, aoff[i] + ks * 16 * PN, PN);
 #pragma unroll
-        for (int j = 0; j < BK; ++j) b[j] = (TTK_BC_WDBG & 8) ? __builtin_bit_cast(bf16x8, make_uint4(c, ks, j, lane)) : tr_frag(buf, boff[j] + ks * 16 * PK, PK);
+        for (int j = 0; j < BK; ++j) b[j] = tr_frag(buf, boff[j] + ks * 16 * PK, PK);
 #pragma unroll
         for (int i = 0; i < BN; ++i)
 #pragma unroll
-          for (int j = 0; j < BK; ++j) {
-            if (TTK_BC_WDBG & 1) { acc[i][j][0] += __uint_as_float(__builtin_bit_cast(uint4, a[i]).x ^ __builtin_bit_cast(uint4, b[j]).y); continue; }
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-          }
+          for (int j = 0; j < BK; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
       }
       store_to(min(c + 1, clast), (c + 1) & 1);  // (the other buffer: last read in step c - 1, every wave has passed the barrier since)
       load(min(c + 2, clast));
@@ -192,7 +173,7 @@ __global__ void __launch_bounds__(512) bc_wgrad_k(const bf16_t* __restrict__ G, 
           }
     }
   }
-  if (wsub == 0 && !((TTK_BC_WDBG & 16) && acc[0][0][0] != 12345.f)) {
+  if (wsub == 0) {
 #pragma unroll
     for (int i = 0; i < BN; ++i)
 #pragma unroll
@@ -201,11 +182,7 @@ __global__ void __launch_bounds__(512) bc_wgrad_k(const bf16_t* __restrict__ G, 
         for (int e = 0; e < 16; ++e) {
           const int row = n0 + (wn * BN + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
           const int col = k0 + (wk * BK + j) * 32 + r;
-#if defined(TTK_BC_WGRAD_ATOMIC)  // (experiment builds: float atomics straight into dW instead of slice tiles + fold; `partial` = dW)
-          unsafeAtomicAdd(partial + (size_t)row * Cin + col, acc[i][j][e]);
-#else
           dst[(size_t)row * Cin + col] = acc[i][j][e];
-#endif
         }
   }
 }
@@ -242,11 +219,6 @@ static bool wgrad_plan(int64_t M, int Cin, int Cout, WPlan& p) {
 
 using namespace ttk;
 using namespace ttk::bc;
-#if defined(TTK_BC_WGRAD_ATOMIC)
-#define TTK_BC_WGRAD_DST dw
-#else
-#define TTK_BC_WGRAD_DST scratch
-#endif
 
 extern "C" {
 
@@ -274,7 +246,7 @@ int ttk_bc_pw_bwd_weight(const void* g, const void* y, const float* bn_pw, const
     constexpr size_t red = KS_ > 1 ? (size_t)8 * (TN32_ / WN_) * (TK32_ / WK_) * 16 * 64 * 4 : 0;                                               \
     (void)allow_big_lds<bc_wgrad_k<TN32_, TK32_, CP_, WN_, WK_, KS_>>();                                                                              \
     hipLaunchKernelGGL((bc_wgrad_k<TN32_, TK32_, CP_, WN_, WK_, KS_>), dim3(grid), dim3(512), sm > red ? sm : red, st, (const bf16_t*)g, (const bf16_t*)y, bn_pw, \
-                       (const bf16_t*)ydw, bn_dw, TTK_BC_WGRAD_DST, M, Cin, Cout, p.rows, p.tiles);                                                      \
+                       (const bf16_t*)ydw, bn_dw, scratch, M, Cin, Cout, p.rows, p.tiles);                                                               \
   } while (0)
   if (p.TN == 64) TTK_BC_WG(2, 1, 128, 2, 1, 4);
   else if (p.TN == 128 && p.TK == 64) TTK_BC_WG(4, 2, 64, 4, 2, 1);
@@ -282,14 +254,12 @@ int ttk_bc_pw_bwd_weight(const void* g, const void* y, const float* bn_pw, const
   else if (p.TK == 128) TTK_BC_WG(8, 4, 32, 4, 2, 1);
   else TTK_BC_WG(8, 8, 32, 4, 2, 1);
 #undef TTK_BC_WG
-#if !defined(TTK_BC_WGRAD_ATOMIC)
   if (!dw) {  // the caller folds the ttk_bc_pw_wgrad_slices tiles of scratch itself (ttk_bc_bn_bwd_finalize_fold)
     TTK_LAUNCH_CHECK("bc_pw_bwd_weight");
   }
   const int64_t n = (int64_t)Cin * Cout;
   if (!launch_fold_rows_fast(scratch, (int)p.slices, n, dw, 1, st))
     hipLaunchKernelGGL(bc_wgrad_fold_k, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, st, scratch, dw, n, (int)p.slices);
-#endif
   TTK_LAUNCH_CHECK("bc_pw_bwd_weight");
 }
 

@@ -16,15 +16,6 @@
 // Tensors are float32 in and out (the entry points' storage flag must be 0: ttk.h).
 #include "ttk_common.h"
 #include <type_traits>
-#ifndef TTK_DW_FWD_U
-#define TTK_DW_FWD_U 6
-#endif
-#ifndef TTK_DW_BWD_U
-#define TTK_DW_BWD_U 4
-#endif
-#ifndef TTK_DW_FWD_U2
-#define TTK_DW_FWD_U2 6
-#endif
 
 namespace ttk {
 
@@ -32,20 +23,15 @@ namespace ttk {
 // apart, a tile row is one contiguous run.  (Over channels-last rows a workgroup touched one 128-byte piece per pixel, 4 C bytes
 // apart: tools/stream_sweep.py, profiles/r03_stream_sweep.txt - 5:1 read:write mix at C = 512: 128-byte pieces 4.9 TB/s, 256-byte
 // pieces 5.5, linear 6.2.  What 64-channel slabs measured there is at dw_tiling().)
-#ifndef TTK_DW_LDS_PIX
-#define TTK_DW_LDS_PIX 368
-#endif
-constexpr int kLdsPixBudget32 = TTK_DW_LDS_PIX;   // (rows) x (W+2) pixels of 128 B each: <= 47 KB -> 3 workgroups per CU (560 -> 2 per CU measured slower)
+constexpr int kLdsPixBudget32 = 368;   // (rows) x (W+2) pixels of 128 B each: <= 47 KB -> 3 workgroups per CU (560 -> 2 per CU measured slower)
 __host__ __device__ constexpr int lds_pix_budget(int SL) { return kLdsPixBudget32 * 32 / SL; }
 __host__ __device__ constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
-#ifndef TTK_DW_WGS_PER_CU
-#define TTK_DW_WGS_PER_CU 3
-#endif
-constexpr int kMaxDwBlocks = 256 * TTK_DW_WGS_PER_CU;   // 3 workgroups per CU x 256 CUs: one resident wave of persistent workgroups
+constexpr int kDwWgsPerCu = 3;
+constexpr int kMaxDwBlocks = 256 * kDwWgsPerCu;   // 3 workgroups per CU x 256 CUs: one resident wave of persistent workgroups
 // staging elements per thread and iteration (forward): their loads are in flight together, and the bytes in flight per CU are
 // what these kernels' throughput follows.  Six fit the 168-register budget of three workgroups per CU when the layer has no
 // residual input to load beside them (the largest layers), four otherwise.
-constexpr int kFwdUSkip = 4, kFwdUPlain = TTK_DW_FWD_U, kFwdUPlain2 = TTK_DW_FWD_U2;
+constexpr int kFwdUSkip = 4, kFwdUPlain = 6, kFwdUPlain2 = 6;
 
 struct DwTiling {
   int SL;                             // channels per slab: 32 | 64
@@ -55,12 +41,6 @@ struct DwTiling {
   int NCT, TW;                        // column tiles per band and their width (stride 1, wide images); else 1, full width
   int carry;                          // a workgroup walks CONSECUTIVE bands of an image and hands their shared staged rows from band to band
 };
-#ifndef TTK_DW_CARRY
-#define TTK_DW_CARRY 1
-#endif
-#ifndef TTK_DW_CARRY_BWD
-#define TTK_DW_CARRY_BWD 1
-#endif
 constexpr int kCarryRegs = 5;  // float4 registers per thread that hand the shared rows from one band to the next
 
 constexpr int kColTileMinW = 48;  // images at least this wide (the 65x65 layer) are tiled in columns too
@@ -92,8 +72,7 @@ inline DwTiling dw_tiling_sl(int B, int H, int W, int C, int stride, bool backwa
   // 33-pixel ones.
   // (stride 2, where the bands share ONE dy row of a tensor a quarter of the input's size, measured slower with the ring: 65 x 65 x 64 259 -> 268 us;
   // stride 1: 33 x 33 x 128 319 -> 284 us, 65 x 65 x 32 217 -> 190 us, profiles/r06_depthwise_backward_carry.txt)
-  t.carry = backward ? (TTK_DW_CARRY_BWD && stride == 1 && (Wo + 2) <= 80)
-                     : (TTK_DW_CARRY && (3 - stride) * (W + 2) * (SL / 4) <= kCarryRegs * kBlock);
+  t.carry = backward ? (stride == 1 && (Wo + 2) <= 80) : ((3 - stride) * (W + 2) * (SL / 4) <= kCarryRegs * kBlock);
   if (!t.carry && stride == 1 && W >= kColTileMinW) {
     t.NCT = (W + kColTile - 1) / kColTile;
     t.TW = (W + t.NCT - 1) / t.NCT;
@@ -227,7 +206,7 @@ enum { kSkipNone = 0, kSkipStored = 1, kSkipRaw = 2 };
 __device__ __forceinline__ const float* only_ptr(const float* p) { return p; }
 
 template <int S, int SKIP, int SL, bool CARRY, typename... BnSkip>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_DW_WGS_PER_CU, TTK_DW_WGS_PER_CU)))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kDwWgsPerCu, kDwWgsPerCu)))
 dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_prev,
                                                           const float* __restrict__ skip_prev, float* __restrict__ a_out,
                                                           const float* __restrict__ w, float* __restrict__ y,
@@ -371,16 +350,12 @@ dw_fwd_tiled_k(const float* __restrict__ yprev, const float* __restrict__ bn_pre
 // LEAN: the block has no residual operands (a_in, skip_prev, skip_grad all null: the strided blocks and dw2_1).  Then the second phase
 // reads one tensor only (yprev) and two pixels per iteration keep 8 KB per workgroup in flight: LEAN handles kLeanPix pixels per
 // iteration with the registers the three absent operands would take.
-#ifndef TTK_DW_BWD_LEAN_PIX
-#define TTK_DW_BWD_LEAN_PIX 4   // stride 1 (168 registers: the cap)
-#endif
-#ifndef TTK_DW_BWD_LEAN_PIX2
-#define TTK_DW_BWD_LEAN_PIX2 4  // stride 2 (6 measured slower: 276 vs 263 us on the 65 x 65 x 64 layer)
-#endif
+constexpr int kLeanPix = 4;   // stride 1 (168 registers: the cap)
+constexpr int kLeanPix2 = 4;  // stride 2 (6 measured slower: 276 vs 263 us on the 65 x 65 x 64 layer)
 // BnSkip (zero or one `const float*`, as in the forward kernel; non-LEAN, a_in null): skip_prev is the RAW convolution output behind the residual
 // operand and bn_skip its BatchNorm constant block.
 template <int S, int SL, bool LEAN, bool CARRY, typename... BnSkip>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TTK_DW_WGS_PER_CU, TTK_DW_WGS_PER_CU)))  // <= 168 VGPRs: 3 workgroups per CU, as the LDS tile allows
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kDwWgsPerCu, kDwWgsPerCu)))  // <= 168 VGPRs: 3 workgroups per CU, as the LDS tile allows
 dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
                                                           const float* __restrict__ bn_dw, const float* __restrict__ w,
                                                           const float* __restrict__ skip_grad,
@@ -459,7 +434,7 @@ dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
     const int nstage = nimg * ((int)PI - (int)ovpix) * kSlabQuads;
     // staged elements per thread and iteration: 2 * kBwdU loads in flight (raw residual operand, stride 1, no ring: two - with its second constant
     // block four spilled 24 bytes and three 8; no layer of the default network runs that instantiation)
-    constexpr int kBwdU = (RAWSKIP && S == 1 && !CARRY) ? TTK_DW_BWD_U - 2 : TTK_DW_BWD_U;
+    constexpr int kBwdU = (RAWSKIP && S == 1 && !CARRY) ? 2 : 4;
     for (int e = tid; e < nstage; e += kBwdU * kBlock) {
       float4 gv[kBwdU], yv[kBwdU];
       bool in[kBwdU];
@@ -495,7 +470,7 @@ dw_bwd_tiled_k(const float* __restrict__ g_dw, const float* __restrict__ y_dw,
     const int npix = nimg * (int)npix1;
     const TileDiv dnp(npix1);
     // NP pixels per thread and iteration: their (up to 3 NP) global loads are issued back to back before any pixel's LDS taps are read
-    constexpr int NP = LEAN ? (S == 2 ? TTK_DW_BWD_LEAN_PIX2 : TTK_DW_BWD_LEAN_PIX) : 2;
+    constexpr int NP = LEAN ? (S == 2 ? kLeanPix2 : kLeanPix) : 2;
     for (int p = slot; p < npix; p += NP * kPixSlots) {
       bool has[NP];
       unsigned imgs[NP], offs[NP];

@@ -19,18 +19,12 @@ constexpr int kStage16 = 64 * (128 + 256);  // 2 planes x 32 B x (BM + BN) rows 
 constexpr int kStride16 = kStage16 + 64;    // the two k16 halves of a producer wave's ds_write_b64 use different banks
 // The LDS ring holds RS super-stages (k32) of 2 k16 stages.  RS = 3 (148 KB): a super-stage is complete one barrier
 // BEFORE the consumers start on it, so they fetch its first fragments under the previous stage's last MFMAs instead of
-// right after the barrier, and the producers' LDS writes of a step may trail into the next one's barrier wait.
-#ifndef TTK_RS
-#define TTK_RS 2
-#endif
+// right after the barrier, and the producers' LDS writes of a step may trail into the next one's barrier wait.  The kernels run RS = 2.
+constexpr int kRingStages = 2;
 // Register sets per producer operand = steps of global loads in flight (each load has D steps to land; cycle stamps and
-// the timing variants of tools/exp/variants.sh showed the producers WAITING for loads that had one step).
-#ifndef TTK_D
-#define TTK_D 1
-#endif
-#ifndef TTK_DW
-#define TTK_DW 1
-#endif
+// timing variants showed the producers WAITING for loads that had one step): of the GEMMs, the weight gradients and the convolutions'
+// 64-row weight gradients.
+constexpr int kSetsGemm = 1, kSetsWgrad = 1, kSetsConvWgrad = 1;
 constexpr int ring_bytes(int rs) { return rs * 2 * kStride16; }
 
 // The consumer side of one block tile: `nks` super-stages (k32) of ds_read_b128 fragments + 3-product MFMAs into
@@ -145,7 +139,7 @@ pw16_k(const float* __restrict__ A0, const float* __restrict__ A1, const float* 
   static_assert((BM == 128 && BN == 256) || (BM == 256 && BN == 128) || (BM == 256 && BN == 64) || (BM == 128 && BN == 64), "tile shapes");
   static_assert(GATHER || (AMODE != AMODE_PLAIN && AMODE != AMODE_PLANES), "plain A operands come from the convolutions");
   constexpr bool PLANES = AMODE == AMODE_PLANES;
-  constexpr int RS = TTK_RS;
+  constexpr int RS = kRingStages;
   constexpr int APL = BM * 32, BPL = BN * 32;  // bytes of one piece plane of a k16 stage
   constexpr int TM = BM / 64, TN = BN / 64;
   constexpr int LDC = BN + 4;
@@ -476,7 +470,7 @@ pw16_wgrad_k(const float* __restrict__ G, const float* __restrict__ Y, const flo
              int64_t M, int Cin, int Cout, int64_t rows_per_slice, const float* __restrict__ x_bound, ConvGeom geo) {
   static_assert((BM + BN == 384 && (BM == 128 || BM == 256)) || (BM == 128 && BN == 128) || (CONV && BM == 64 && (BN == 256 || BN == 192)),
                 "128x256, 256x128, 128x128 or (convolutions) 64x256, 64x192");
-  constexpr int RS = TTK_RS;
+  constexpr int RS = kRingStages;
   constexpr int APL = BM * 32, BPL = BN * 32;
   constexpr int TM = BM / 64, TN = BN / 64;
   // small convolution tiles: a smaller ring, so that two workgroups share a CU (twice the producer waves - their VALU work
@@ -863,9 +857,9 @@ bool launch_f16_wgrad(const float* g, const float* y, const float* bn_pw, const 
   wgrad_slices(M, tiles, slices, rows);
   const dim3 grid(tiles, (unsigned)slices);
   if (!wide && Cout % 256 != 0)
-    hipLaunchKernelGGL((pw16_wgrad_k<128, 128, TTK_DW>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
+    hipLaunchKernelGGL((pw16_wgrad_k<128, 128, kSetsWgrad>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
   else if (wide)
-    hipLaunchKernelGGL((pw16_wgrad_k<128, 256, TTK_DW>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
+    hipLaunchKernelGGL((pw16_wgrad_k<128, 256, kSetsWgrad>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
   else  // (one register set: two spill)
     hipLaunchKernelGGL((pw16_wgrad_k<256, 128, 1>), grid, dim3(512), 0, st, g, y, bn_pw, ydw, bn_dw, dw, partial, M, Cin, Cout, rows, nullptr, ConvGeom{});
   if (partial) {
@@ -906,14 +900,14 @@ bool launch_f16_gemm(const float* A0, const float* A1, const float* bnA, const f
   }
   if (Nout >= 256 && Nout % 256 == 0) {
     const unsigned tiles = (unsigned)(ceil_div(M, 128) * (Nout / 256));
-    hipLaunchKernelGGL((pw16_k<128, 256, AM, EM, TTK_D>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
+    hipLaunchKernelGGL((pw16_k<128, 256, AM, EM, kSetsGemm>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
                        Nout, nullptr, ConvGeom{});
     return true;
   }
   if (Nout == 128) {
     const unsigned tiles = (unsigned)ceil_div(M, 256);
-    constexpr int D = (MODE == SMODE_DGRAD || TTK_D > 2) ? 1 : TTK_D;  // eight A rows per thread: more sets spill
-    hipLaunchKernelGGL((pw16_k<256, 128, AM, EM, D>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
+    // (eight A rows per thread: more than one set spill)
+    hipLaunchKernelGGL((pw16_k<256, 128, AM, EM, 1>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, const_cast<float*>(bnE), part, M, K,
                        Nout, nullptr, ConvGeom{});
     return true;
   }
@@ -950,13 +944,10 @@ bool launch_conv_wgrad16(const float* g, const float* y, const float* bn, const 
   int64_t slices, rows;
   conv_wgrad_plan(M, Cout, ncols, tiles, slices, rows);
   const dim3 grid(tiles, (unsigned)slices);
-#ifndef TTK_DC
-#define TTK_DC 1
-#endif
   // y == nullptr: g holds dy as two fp16 planes [M][Cout] (h, then l)
   const float* yy = y ? y : reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(g) + M * Cout);
 #define TTK_WGRAD_LAUNCH(BM_, BN_, PLAIN_)                                                                                                      \
-  hipLaunchKernelGGL((pw16_wgrad_k<BM_, BN_, (BM_ == 64 ? TTK_DC : 1), true, false, PLAIN_>), grid, dim3(512), 0, st, g, yy, bn, a_in, nullptr, dw, partial, M, ncols, \
+  hipLaunchKernelGGL((pw16_wgrad_k<BM_, BN_, (BM_ == 64 ? kSetsConvWgrad : 1), true, false, PLAIN_>), grid, dim3(512), 0, st, g, yy, bn, a_in, nullptr, dw, partial, M, ncols, \
                      Cout, rows, a_bound, geo)
   if (narrow && conv_wgrad_bn(Cout, ncols) == 192) { if (y) TTK_WGRAD_LAUNCH(64, 192, false); else TTK_WGRAD_LAUNCH(64, 192, true); }
   else if (narrow) { if (y) TTK_WGRAD_LAUNCH(64, 256, false); else TTK_WGRAD_LAUNCH(64, 256, true); }

@@ -23,66 +23,13 @@
 #include "split16.h"
 #include <type_traits>
 
-// TTK_M_NOPK=1 (experiment builds): this file's kernels without packed fp32 instructions.  Measured (profiles/r04_rowblock_gemm_variants.txt):
-// pw16m_k 5 % SLOWER (forward 87.8 vs 82.9 us, data gradient 103 vs 96) - beside MFMAs the NUMBER of vector instructions is what costs.
-#ifndef TTK_M_NOPK
-#define TTK_M_NOPK 0
-#endif
-#if TTK_M_NOPK && defined(__HIP_DEVICE_COMPILE__)
-// every function of this translation unit (kernels, their lambdas, the inline helpers): same target features, so everything still inlines
-#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
-#endif
+// The kernels of this file keep their packed fp32 instructions: without them (target("no-packed-fp32-ops") on every function) pw16m_k
+// measured 5 % SLOWER (forward 87.8 vs 82.9 us, data gradient 103 vs 96: profiles/r04_rowblock_gemm_variants.txt) - beside MFMAs the
+// NUMBER of vector instructions is what costs.
 
 namespace ttk {
 
 enum { RMODE_FWD = 0, RMODE_DGRAD = 1 };
-// Experiment builds only (tools/exp/build_variants.sh; the product is built with all of them at their defaults):
-//   TTK_R_DBG   timing-only bits, results wrong by construction: 1 no A loads | 2 no LDS-DMA | 4 no MFMAs | 8 no epilogue |
-//               16 the data gradient's epilogue does not read its mask operand | 32 the producers store their rows unconverted |
-//               64 the producers store nothing (barriers only) | 128 the consumers read no fragments (MFMAs on stale registers)
-//   TTK_R_PPRIO / TTK_R_CPRIO   s_setprio of the producer / consumer waves
-#ifndef TTK_R_DBG
-#define TTK_R_DBG 0
-#endif
-#ifndef TTK_R_PPRIO
-#define TTK_R_PPRIO 3
-#endif
-#ifndef TTK_R_CPRIO
-#define TTK_R_CPRIO 0
-#endif
-//   TTK_R_SETS  register sets of the producers' A rows: 2 (default) = the rows of step s + 2 are requested before step s + 1 is
-//               converted; 1 = round 3's schedule (rows requested one step ahead, after the conversion)
-#ifndef TTK_R_SETS
-#define TTK_R_SETS 2
-#endif
-//   TTK_R_GPS_F / TTK_R_NSLOT_F, TTK_R_GPS_D / TTK_R_NSLOT_D   groups per step and register slots of the producers' pipeline
-//               (forward / data gradient; see pw16r_k)
-//   TTK_R_MERGED 1 (default) = pw16m_k (eight waves that convert and multiply) for the data gradient, 2 = for the forward too,
-//                0 = pw16r_k (eight MFMA + four producer waves) everywhere
-//   TTK_M_FENCE  1 = a scheduling fence behind every conversion part of pw16m_k
-#ifndef TTK_R_MERGED
-#define TTK_R_MERGED 1
-#endif
-#ifndef TTK_M_FENCE
-#define TTK_M_FENCE 1
-#endif
-//   TTK_M_MIX    1 (default) = low pieces by v_fma_mix, 0 = convert back, subtract, convert
-#ifndef TTK_M_MIX
-#define TTK_M_MIX 1
-#endif
-
-#ifndef TTK_R_GPS_F
-#define TTK_R_GPS_F 1
-#endif
-#ifndef TTK_R_NSLOT_F
-#define TTK_R_NSLOT_F 2
-#endif
-#ifndef TTK_R_GPS_D
-#define TTK_R_GPS_D 2
-#endif
-#ifndef TTK_R_NSLOT_D
-#define TTK_R_NSLOT_D 3
-#endif
 template <int N, typename F, int I = 0>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) {
@@ -90,15 +37,7 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for<N, F, I + 1>(static_cast<F&&>(f));
   }
 }
-constexpr int kRDbg = TTK_R_DBG;
-__device__ __forceinline__ f32x16 rmfma(f16x8 a, f16x8 b, f32x16 c) {
-  if constexpr (kRDbg & 4) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-}
+__device__ __forceinline__ f32x16 rmfma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 constexpr int kRBN = 256;  // tile width
 
 // raw s_barrier (no vmcnt drain: the producers keep global loads in flight across it) fenced against compiler motion of LDS accesses
@@ -107,20 +46,6 @@ __device__ __forceinline__ void rbarrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-
-#if defined(TTK_R_STAMP)
-// Experiment builds only (tools/exp): cycle accounting per wave.  A stamp is s_memtime behind the lgkmcnt(0) a barrier needs anyway.
-__device__ unsigned long long g_r_stamps[2048 * 12 * 8];
-#define TTK_STAMP(t) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
-#define TTK_RSTAMP(t) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
-__device__ __forceinline__ void rbarrier_s(unsigned long long& wait) {
-  unsigned long long a, b;
-  TTK_STAMP(a);
-  __builtin_amdgcn_s_barrier();
-  TTK_STAMP(b);
-  wait += b - a;
-}
-#endif
 
 // Low piece l = fp16(x - h) of two values whose high pieces are the halves of `h`: v_fma_mixlo/hi_f16 take the fp16 half as a source
 // of an fp32 fma and round the result to fp16 once - the value of (cvt_f32_f16, subtract, cvt_pk_f16_f32) in two instructions
@@ -186,14 +111,6 @@ __device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, float* 
     if (bnE) emean = ld4(bnE + col);  // forward: bnE is the statistics pivot [Nout] (ttk.h), the sums are those of y - pivot
   }
   float4 s1 = f4(0.f), s2 = f4(0.f);
-  if constexpr (kRDbg & 8) {
-    if (wave < 8) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[i][j]));
-    }
-  } else {
   // The data gradient's mask operand (raw depthwise output) is requested one group of rows ahead into the other of two register
   // buffers: a chunk's later groups and the next chunk's first group while the current group is processed (the registers of the
   // accumulators already parked are free by then), the tile's first group right after chunk 0 is parked.  Requested inside the
@@ -210,8 +127,7 @@ __device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, float* 
         const int cr = rg + NW * (g * NRG + u);
         const int64_t grow = tile_row(c, cr);
         ev[idx & 1][u] = f4(0.f);
-        if constexpr (!(kRDbg & 16))
-          if (cr < CH && grow < m_end) ev[idx & 1][u] = ld4(E0 + act_off(grow, col, M));
+        if (cr < CH && grow < m_end) ev[idx & 1][u] = ld4(E0 + act_off(grow, col, M));
       }
     }
   };
@@ -263,7 +179,6 @@ __device__ __forceinline__ void r_epilogue(unsigned char* lds, Acc& acc, float* 
     });
     __syncthreads();  // the row pass is done: the next chunk may be parked
   });
-  }
   if (part) {  // one row of partial sums per tile: NW row groups folded in a fixed order
     st4(red + (rg * 2 + 0) * kRBN + 4 * c4, s1);
     st4(red + (rg * 2 + 1) * kRBN + 4 * c4, s2);
@@ -319,18 +234,10 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
     }
     __syncthreads();
   }
-#if defined(TTK_R_STAMP)
-  unsigned long long st_t0, st_r0, st_wait = 0, st_aux = 0, st_loop0 = 0, st_loop1 = 0, st_x, st_y;
-  TTK_STAMP(st_t0);
-  TTK_RSTAMP(st_r0);
-#define TTK_RB() rbarrier_s(st_wait)
-#else
-#define TTK_RB() rbarrier()
-#endif
 
   if (wave >= 8) {
     // ---------------- producers: A through registers (BatchNorm form, split, ds_write), B by LDS-DMA ----------------
-    __builtin_amdgcn_s_setprio(TTK_R_PPRIO);
+    __builtin_amdgcn_s_setprio(3);
     const int pt = tid - 512;
     const int row0 = pt >> 3, kq8 = pt & 7;  // 32 rows per pass; 8 lanes x 16 B = one 128-byte row segment
     const int sub = kq8 >> 2, chunk = (kq8 >> 1) & 1, o8 = (kq8 & 1) * 8;
@@ -342,8 +249,8 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
     // latency + conversion + issue) per step: 3 700 cycles measured against 2 304 of matrix work, the consumers waiting 1 000 at
     // the barrier of every step (profiles/r04_rowblock_stamps.txt).  The forward keeps two whole sets (budget: two steps); the data
     // gradient, whose rows are two tensors, three half sets (72 registers at RBLK = 6; budget: a step and a half).
-    constexpr int GPS = TTK_R_SETS == 1 ? 1 : (FWD ? TTK_R_GPS_F : TTK_R_GPS_D);
-    constexpr int NSLOT = TTK_R_SETS == 1 ? 1 : (FWD ? TTK_R_NSLOT_F : TTK_R_NSLOT_D);
+    constexpr int GPS = FWD ? 1 : 2;    // groups per step
+    constexpr int NSLOT = FWD ? 2 : 3;  // register slots
     static_assert(AP % GPS == 0 && (GPS & (GPS - 1)) == 0, "groups per step: a power of two that divides the row passes");
     constexpr int G = AP / GPS;
     constexpr int UNR = NSLOT % GPS == 0 ? NSLOT : (GPS % NSLOT == 0 ? GPS : NSLOT * GPS);  // groups per unrolled round: slot and half are compile-time
@@ -366,16 +273,9 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
 #pragma unroll
       for (int u = 0; u < G; ++u) {
         const int i = hf * G + u;
-        if constexpr (kRDbg & 1) {
-          f32x4 t0 = ra0[slot][u], t1 = ra1[slot][FWD ? 0 : u];  // (copies: clang rejects captured arrays as asm operands in this lambda)
-          asm volatile("" : "+v"(t0), "+v"(t1));
-          ra0[slot][u] = t0;
-          ra1[slot][FWD ? 0 : u] = t1;
-        } else {
-          const unsigned o = ((live >> i) & 1u) ? aoff0 + (unsigned)(i * 32 * kCB) : (unsigned)(kq8 * 4);  // (dead rows - pass 0's too - read row 0 of the tile)
-          ra0[slot][u] = rbuf_ld4(r0, o);
-          if constexpr (!FWD) ra1[slot][u] = rbuf_ld4(r1, o);
-        }
+        const unsigned o = ((live >> i) & 1u) ? aoff0 + (unsigned)(i * 32 * kCB) : (unsigned)(kq8 * 4);  // (dead rows - pass 0's too - read row 0 of the tile)
+        ra0[slot][u] = rbuf_ld4(r0, o);
+        if constexpr (!FWD) ra1[slot][u] = rbuf_ld4(r1, o);
       }
     };
     auto conv_g = [&](int ks, auto hfc, auto slotc) {  // BatchNorm form, split, ds_write of group hf of step ks
@@ -399,15 +299,6 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
         // the padding rows of a block (RT = 162 of 192) are never stored; as ZEROS they also cost the matrix pipe far less power than
         // copies of real rows would (the chip holds a higher clock on zero operands), and these kernels run at the power limit
         if (!((live >> i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (kRDbg & 64) {
-          const f32x4 t0 = v;
-          asm volatile("" ::"v"(t0));
-        } else if constexpr (kRDbg & 32) {
-          unsigned char* dst = S + swz16(row0 + 32 * i, chunk);
-          const f32x4 w = ra0[slot][u];
-          *reinterpret_cast<uint2*>(dst) = make_uint2(__float_as_uint(w.x), __float_as_uint(w.y));
-          *reinterpret_cast<uint2*>(dst + APL) = make_uint2(__float_as_uint(w.z), __float_as_uint(w.w));
-        } else
         split_store16(v, S + swz16(row0 + 32 * i, chunk), APL);
       }
     };
@@ -424,37 +315,19 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
         using SL = std::integral_constant<int, d % NSLOT>;
         const int n = n0 + d;
         if (n < NG) {
-#if defined(TTK_R_STAMP)
-          TTK_STAMP(st_x);
-#endif
           conv_g(n / GPS, HF{}, SL{});
-#if defined(TTK_R_STAMP)
-          __builtin_amdgcn_sched_barrier(0);
-          TTK_STAMP(st_y);
-          if (n >= GPS) st_aux += st_y - st_x;
-#endif
           // (UNR is a multiple of GPS and of NSLOT, so group n + NSLOT has half (d + NSLOT) % GPS and goes to slot d % NSLOT)
           if (n + NSLOT < NG) load_g((n + NSLOT) / GPS, std::integral_constant<int, (d + NSLOT) % GPS>{}, SL{});
           if constexpr (d % GPS == GPS - 1) {
             __builtin_amdgcn_sched_barrier(0);
-            TTK_RB();  // stage n / GPS is in LDS; the consumers are done with the stage before it
-#if defined(TTK_R_STAMP)
-            if (n / GPS == 0) {
-              TTK_STAMP(st_loop0);
-              st_wait = 0;
-            }
-#endif
+            rbarrier();  // stage n / GPS is in LDS; the consumers are done with the stage before it
           }
         }
       });
     }
-    TTK_RB();  // the consumers are done with the last stage: the ring is free for the epilogue
-#if defined(TTK_R_STAMP)
-    TTK_STAMP(st_loop1);
-#endif
+    rbarrier();  // the consumers are done with the last stage: the ring is free for the epilogue
   } else {
     // ---------------- consumers: ds_read_b128 fragments + three piece products per block pair ----------------
-    if constexpr (TTK_R_CPRIO != 0) __builtin_amdgcn_s_setprio(TTK_R_CPRIO);
     const int lane = tid & 63, wm = wave / WN, wn = wave % WN;
     const int r = lane & 31, h = lane >> 5;
     constexpr bool HOLD_A = TM <= TN;  // hold the smaller fragment set of a k16 stage in registers, stream the other
@@ -482,7 +355,6 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
     // fragment reads into lgkmcnt(0); M0 = the wave-uniform LDS destination, restored afterwards; the data is waited for by hand)
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     auto dma_b = [&](int ks) {  // weight planes of k32 step ks -> ring slot ks & 1
-      if constexpr (kRDbg & 2) return;
       const uint16_t* sp = bsrc + (int64_t)ks * 2 * Nout * 16;
       const unsigned d = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((ks & 1) * 2 * kStr + bdst));
 #pragma unroll
@@ -496,23 +368,11 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
     };
     dma_b(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TTK_RB();  // stage 0 is in LDS
-#if defined(TTK_R_STAMP)
-    TTK_STAMP(st_loop0);
-    st_wait = 0;
-#endif
+    rbarrier();  // stage 0 is in LDS
     // Software pipeline of a k32 step (two k16 stages): the stream fragment of block x + 1 is requested before the MFMAs of block x,
     // and the hold fragments of the NEXT k16 stage replace the current ones as soon as the last block's MFMAs have read them - so
     // inside a step no MFMA waits for a read that was issued right before it; only the first fragments after the barrier are exposed.
-    auto rd = [&](const unsigned char* S, int plane_bytes, int off, int p) {
-      if constexpr (kRDbg & 128) {
-        f16x8 z = hold[0][0];
-        asm volatile("" : "+v"(z));
-        return z;
-      } else {
-        return *reinterpret_cast<const f16x8*>(S + p * plane_bytes + off);
-      }
-    };
+    auto rd = [&](const unsigned char* S, int plane_bytes, int off, int p) { return *reinterpret_cast<const f16x8*>(S + p * plane_bytes + off); };
     for (int it = 0; it < nks; ++it) {
       if (it + 1 < nks) dma_b(it + 1);  // slot (it + 1) & 1 was released by the barrier just passed
       const unsigned char* S0 = lds + (it & 1) * 2 * kStr;
@@ -555,35 +415,11 @@ __global__ void __launch_bounds__(768) pw16r_k(const float* __restrict__ A0, con
           }
         }
       }
-#if defined(TTK_R_STAMP)
-      TTK_STAMP(st_x);
-#endif
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of stage it + 1 have landed
-#if defined(TTK_R_STAMP)
-      TTK_STAMP(st_y);
-      st_aux += st_y - st_x;
-#endif
-      TTK_RB();  // done with stage `it` (its fragments are in registers, its slot may be refilled); stage it + 1 is in LDS
+      rbarrier();  // done with stage `it` (its fragments are in registers, its slot may be refilled); stage it + 1 is in LDS
     }
-#if defined(TTK_R_STAMP)
-    TTK_STAMP(st_loop1);
-#endif
   }
-#undef TTK_RB
   r_epilogue<RBLK, MODE, 12>(lds, acc, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
-#if defined(TTK_R_STAMP)
-  {
-    unsigned long long st_t1, st_r1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TTK_STAMP(st_t1);
-    TTK_RSTAMP(st_r1);
-    if ((tid & 63) == 0 && blockIdx.x < 2048) {
-      unsigned long long* d = g_r_stamps + ((size_t)blockIdx.x * 12 + wave) * 8;
-      d[0] = st_loop0 - st_t0; d[1] = st_loop1 - st_loop0; d[2] = st_t1 - st_loop1; d[3] = st_wait; d[4] = st_aux; d[5] = st_r1 - st_r0; d[6] = st_t1 - st_t0;
-      d[7] = st_r0;
-    }
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -607,21 +443,17 @@ struct MGeo {
   static constexpr int kSmem = G::kRing + G::kCst > kEpi ? G::kRing + G::kCst : kEpi;
 };
 
-#ifndef TTK_M_M16
-#define TTK_M_M16 1
-#endif
-// M16 (default): the products on v_mfma_f32_16x16x32_f16 - a k32 step in ONE instruction per 16 x 16 block, same LDS image, same fragment
-// reads, same cycles per flop as 32x32x16 - for two reasons: the 16-row blocks that lie wholly behind the end of the row block are
+// It runs the data gradient at tile heights 4 and 6 (launch_f16r_gemm).  The products are on v_mfma_f32_16x16x32_f16 - a k32 step in
+// ONE instruction per 16 x 16 block, same LDS image, same fragment reads, same cycles per flop as 32x32x16 - for two reasons: the 16-row blocks that lie wholly behind the end of the row block are
 // skipped (RT = 162 of a 192-row tile: the last of the twelve, i.e. 8 % of the matrix work), and the guide measures the 16 x 16 shape at a
 // higher clock under the power limit.  Measured: data gradient of 512 x 512 99.9 -> 97.2 us before the skip (profiles/r04_rowblock_gemm_variants.txt)
-template <int RBLK, int MODE, bool M16>
+template <int RBLK>
 __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, const float* __restrict__ A1, const float* __restrict__ bnA,
                                                const uint16_t* __restrict__ Bq, const float* __restrict__ wmax, float* __restrict__ out,
                                                const float* __restrict__ E0, const float* __restrict__ bnE, float* __restrict__ part, int64_t M,
                                                int K, int Nout, int RT) {
   using G = RGeo<RBLK>;
   constexpr int RB = G::RB, WM = G::WM, WN = G::WN, TM = G::TM, TN = G::TN, APL = G::APL, BPL = G::BPL, kStr = G::kStr;
-  constexpr bool FWD = MODE == RMODE_FWD;
   __shared__ __attribute__((aligned(16))) unsigned char lds[MGeo<RBLK>::kSmem];
 
   const int tid = threadIdx.x;
@@ -635,17 +467,15 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   const int n0 = bx * kRBN;
   const int nks = K / 32;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const float sa = pow2_scale(bnA[(size_t)TTK_BN_AUX * K + (FWD ? TTK_AUX_ACT_BOUND : TTK_AUX_DY_BOUND)]);
+  const float sa = pow2_scale(bnA[(size_t)TTK_BN_AUX * K + TTK_AUX_DY_BOUND]);
   const float sb = pow2_scale(*wmax);
-  f32x16 acc[M16 ? 1 : TM][M16 ? 1 : TN];
-  f32x4 acc16[M16 ? 2 * TM : 1][M16 ? 2 * TN : 1];
-  // per-channel constants of the A operand, once per tile: [scale S_a | mean | beta S_a] (forward), [ga S_a | gmean | gb S_a | mean] (data gradient)
+  f32x4 acc16[2 * TM][2 * TN];  // 16 x 16 blocks
+  // per-channel constants of the A operand, once per tile: [ga S_a | gmean | gb S_a | mean]
   float* cst = reinterpret_cast<float*>(lds + G::kRing);
   {
-    constexpr int NQ = FWD ? 3 : 4;
-    for (int i = tid * 4; i < NQ * K; i += 512 * 4) {
+    for (int i = tid * 4; i < 4 * K; i += 512 * 4) {
       const int j = i / K, c = i - j * K;
-      const int row = FWD ? (j == 0 ? TTK_BN_SCALE : (j == 1 ? TTK_BN_MEAN : TTK_BN_BETA)) : (j == 0 ? TTK_BN_GA : (j == 1 ? TTK_BN_GMEAN : (j == 2 ? TTK_BN_GB : TTK_BN_MEAN)));
+      const int row = j == 0 ? TTK_BN_GA : (j == 1 ? TTK_BN_GMEAN : (j == 2 ? TTK_BN_GB : TTK_BN_MEAN));
       float4 v = ld4(bnA + (size_t)row * K + c);
       if (j == 0 || j == 2) v = make_float4(v.x * sa, v.y * sa, v.z * sa, v.w * sa);
       st4(cst + i, v);
@@ -657,8 +487,8 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   const int row0 = tid >> 3, kq8 = tid & 7;  // 64 rows per pass; 8 lanes x 16 B = one 128-byte row segment
   const int sub_ = kq8 >> 2, chunk = (kq8 >> 1) & 1, o8 = (kq8 & 1) * 8;
   constexpr int AP = RB / 64;                 // row passes per stage
-  constexpr int NA = AP * (FWD ? 1 : 2);      // vector-memory loads per thread and stage
-  f32x4 ra0[2][AP] = {}, ra1[2][FWD ? 1 : AP] = {};
+  constexpr int NA = AP * 2;                  // vector-memory loads per thread and stage (two tensors)
+  f32x4 ra0[2][AP] = {}, ra1[2][AP] = {};
   unsigned live = 0u;  // bit u: pass u's row lies inside the row block
 #pragma unroll
   for (int u = 0; u < AP; ++u) live |= (m0 + row0 + 64 * u < m_end ? 1u : 0u) << u;
@@ -672,22 +502,15 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   auto load_a = [&](int ks, auto setc) {  // rows of stage ks -> register set
     constexpr int set = decltype(setc)::value;
     const __amdgpu_buffer_rsrc_t r0 = rbuf(A0 + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
-    const __amdgpu_buffer_rsrc_t r1 = rbuf((FWD ? (const float*)nullptr : A1) + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
+    const __amdgpu_buffer_rsrc_t r1 = rbuf(A1 + ((size_t)ks * act_block_stride(M) + (size_t)m0 * kCB));
 #pragma unroll
     for (int u = 0; u < AP; ++u) {
-      if constexpr (kRDbg & 1) {
-        f32x4 t0 = ra0[set][u], t1 = ra1[set][FWD ? 0 : u];
-        asm volatile("" : "+v"(t0), "+v"(t1));
-        ra0[set][u] = t0;
-        ra1[set][FWD ? 0 : u] = t1;
-      } else {
-        const unsigned o = ((live >> u) & 1u) ? aoff0 + (unsigned)(u * 64 * kCB) : (unsigned)(kq8 * 4);
-        ra0[set][u] = rbuf_ld4(r0, o);
-        if constexpr (!FWD) ra1[set][u] = rbuf_ld4(r1, o);
-      }
+      const unsigned o = ((live >> u) & 1u) ? aoff0 + (unsigned)(u * 64 * kCB) : (unsigned)(kq8 * 4);
+      ra0[set][u] = rbuf_ld4(r0, o);
+      ra1[set][u] = rbuf_ld4(r1, o);
     }
   };
-  // Conversion of one row pass in two parts (a part sits behind every second MFMA triple): part 0 = BatchNorm form + high pieces, part 1
+  // Conversion of one row pass in two parts (a part sits behind every fourth MFMA triple): part 0 = BatchNorm form + high pieces, part 1
   // = low pieces + the two ds_write_b64.  `pv`, `ph` carry a pass from part 0 to part 1.
   f32x4 cc0 = {}, cq1 = {}, cc2 = {}, cq3 = {};  // the stage's per-channel constants (from LDS, S_a folded in)
   f32x4 pv = {};
@@ -695,22 +518,16 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   auto conv_consts = [&](int ks) {
     const float* cs = cq + ks * 32;
     cc0 = *reinterpret_cast<const f32x4*>(cs); cq1 = *reinterpret_cast<const f32x4*>(cs + K); cc2 = *reinterpret_cast<const f32x4*>(cs + 2 * K);
-    if constexpr (!FWD) cq3 = *reinterpret_cast<const f32x4*>(cs + 3 * K);
+    cq3 = *reinterpret_cast<const f32x4*>(cs + 3 * K);
   };
   int conv_ks = 0;
   auto conv_part = [&](auto setc, auto slotc, auto ppc) {
     constexpr int set = decltype(setc)::value, slot = decltype(slotc)::value, pp = decltype(ppc)::value, u = pp >> 1;
     if constexpr ((pp & 1) == 0) {
-      // (the data gradient re-reads its four constant quads per row pass: held through the step they cost 16 registers and the
-      // kernel spilled inside its loop)
-      if constexpr (!FWD) conv_consts(conv_ks);
-      f32x4 v;
-      if constexpr (FWD) {
-        v = cc0 * (ra0[set][u] - cq1) + cc2;
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-      } else {
-        v = cc0 * (ra0[set][u] - cq1) + cc2 * (ra1[set][u] - cq3);
-      }
+      // (the four constant quads are re-read per row pass: held through the step they cost 16 registers and the kernel spilled
+      // inside its loop)
+      conv_consts(conv_ks);
+      f32x4 v = cc0 * (ra0[set][u] - cq1) + cc2 * (ra1[set][u] - cq3);
       if (m0 + 64 * u + 63 >= m_end) {  // (uniform: only the pass that holds the end of the row block masks its rows)
         if (!((live >> u) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -718,59 +535,37 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
       pv = v;
       ph = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
     } else {
-#if TTK_M_MIX
       const unsigned l01 = rlow2(ph.x, pv.x, pv.y), l23 = rlow2(ph.y, pv.z, pv.w);
-#else
-      const f32x2 f01 = __builtin_convertvector(__builtin_bit_cast(f16x2, ph.x), f32x2), f23 = __builtin_convertvector(__builtin_bit_cast(f16x2, ph.y), f32x2);
-      const unsigned l01 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{pv.x - f01.x, pv.y - f01.y}, f16x2));
-      const unsigned l23 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{pv.z - f23.x, pv.w - f23.y}, f16x2));
-#endif
       unsigned char* dst = wbase + slot * 2 * kStr + u * 64 * 32;
-      if constexpr (!(kRDbg & 64)) {
-        *reinterpret_cast<uint2*>(dst) = ph;
-        *reinterpret_cast<uint2*>(dst + APL) = make_uint2(l01, l23);
-      } else {
-        asm volatile("" ::"v"(l01), "v"(l23));
-      }
+      *reinterpret_cast<uint2*>(dst) = ph;
+      *reinterpret_cast<uint2*>(dst + APL) = make_uint2(l01, l23);
     }
   };
 
   // ---- this wave's blocks of the tile ----
   const int lane = tid & 63, wm = wave / WN, wn = wave % WN;
+  static_assert(TM * TN == RBLK && 2 * AP == RBLK, "4 RBLK MFMA triples per step, one of the 2 AP conversion parts behind every fourth");
+  // Kept from the 32x32x16 form this kernel no longer has, and dead: the offsets of pw16r_k's held fragments.  Nothing reads them and no
+  // instruction computes them, but without these lines hipcc folds the address arithmetic of wm and wn below in another order and the
+  // kernels' scalar prologue comes out different (profiles/compile_switches_codegen.txt); the kernels stay as they were measured.
   const int r = lane & 31, h = lane >> 5;
-  constexpr bool HOLD_A = TM <= TN;  // hold the smaller fragment set of a k16 stage in registers, stream the other
-  constexpr int TH = HOLD_A ? TM : TN, TS = HOLD_A ? TN : TM;
-  constexpr int HPL = HOLD_A ? APL : BPL, SPL = HOLD_A ? BPL : APL;
-  static_assert(2 * TS * TH == 2 * RBLK && 2 * AP == RBLK, "one conversion part behind every second MFMA triple");
-  int hold_off[TH], strm_off[TS];
+  constexpr bool HOLD_A = TM <= TN;
+  constexpr int TH = HOLD_A ? TM : TN;
+  int hold_off[TH];
 #pragma unroll
   for (int x = 0; x < TH; ++x) hold_off[x] = HOLD_A ? swz16(wm * (32 * TM) + x * 32 + r, h) : 2 * APL + swz16(wn * (32 * TN) + x * 32 + r, h);
 #pragma unroll
-  for (int x = 0; x < TS; ++x) strm_off[x] = HOLD_A ? 2 * APL + swz16(wn * (32 * TN) + x * 32 + r, h) : swz16(wm * (32 * TM) + x * 32 + r, h);
-  if constexpr (!M16) {
+  for (int i = 0; i < 2 * TM; ++i)
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 2 * TM; ++i)
-#pragma unroll
-      for (int j = 0; j < 2 * TN; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  f16x8 hold[TH][2] = {}, strm[2][2] = {};
+    for (int j = 0; j < 2 * TN; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // 16 x 16 x 32 fragments: lane l holds row l & 15, k = 8 (l >> 4) .. + 7 of the k32 step: k16 stage (l >> 5), 16-byte chunk (l >> 4) & 1
-  int a16_off[M16 ? 2 * TM : 1], b16_off[M16 ? 2 * TN : 1];
+  int a16_off[2 * TM], b16_off[2 * TN];
   const int live_rows16 = (int)(m_end - m0) - wm * (32 * TM);  // rows of this wave's strip inside the row block
-  if constexpr (M16) {
-    const int r16 = lane & 15, g4 = lane >> 4;
+  const int r16 = lane & 15, g4 = lane >> 4;
 #pragma unroll
-    for (int i = 0; i < 2 * TM; ++i) a16_off[i] = (g4 >> 1) * kStr + swz16(wm * (32 * TM) + i * 16 + r16, g4 & 1);
+  for (int i = 0; i < 2 * TM; ++i) a16_off[i] = (g4 >> 1) * kStr + swz16(wm * (32 * TM) + i * 16 + r16, g4 & 1);
 #pragma unroll
-    for (int j = 0; j < 2 * TN; ++j) b16_off[j] = (g4 >> 1) * kStr + 2 * APL + swz16(wn * (32 * TN) + j * 16 + r16, g4 & 1);
-  }
+  for (int j = 0; j < 2 * TN; ++j) b16_off[j] = (g4 >> 1) * kStr + 2 * APL + swz16(wn * (32 * TN) + j * 16 + r16, g4 & 1);
   // LDS-DMA of the weight planes (as pw16r_k): wave w moves pieces 4 w .. 4 w + 3 of a k32 step - k16 stage w >> 2, plane (w >> 1) & 1,
   // rows 128 (w & 1) .. + 127 - right after the barrier that freed the slot, and waits for them before the barrier that publishes it.
   const int64_t bplane = (int64_t)K * Nout;
@@ -778,7 +573,6 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   const int bdst = (wave >> 2) * kStr + 2 * APL + ((wave >> 1) & 1) * BPL + (wave & 1) * 4096;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
   auto dma_b = [&](int ks, int slot) {  // weight planes of k32 step ks -> ring slot
-    if constexpr (kRDbg & 2) return;
     const uint16_t* sp = bsrc + (int64_t)ks * 2 * Nout * 16;
     const unsigned d = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(slot * 2 * kStr + bdst));
 #pragma unroll
@@ -790,26 +584,10 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
                    : "memory");
     }
   };
-  auto rd = [&](const unsigned char* S, int plane_bytes, int off, int p) {
-    if constexpr (kRDbg & 128) {
-      f16x8 z = hold[0][0];
-      asm volatile("" : "+v"(z));
-      return z;
-    } else {
-      return *reinterpret_cast<const f16x8*>(S + p * plane_bytes + off);
-    }
-  };
+  auto rd = [&](const unsigned char* S, int plane_bytes, int off, int p) { return *reinterpret_cast<const f16x8*>(S + p * plane_bytes + off); };
   using P0 = std::integral_constant<int, 0>;
   using P1 = std::integral_constant<int, 1>;
 
-#if defined(TTK_R_STAMP)
-  unsigned long long st_t0, st_r0, st_wait = 0, st_aux = 0, st_loop0 = 0, st_loop1 = 0, st_x, st_y;
-  TTK_STAMP(st_t0);
-  TTK_RSTAMP(st_r0);
-#define TTK_RB() rbarrier_s(st_wait)
-#else
-#define TTK_RB() rbarrier()
-#endif
   // ---- prologue: stage 0 into ring slot 0 (nothing to hide it under), the rows of stages 1 and 2 requested ----
   load_a(0, P0{});
   if (nks > 1) load_a(1, P1{});
@@ -823,11 +601,7 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  TTK_RB();  // stage 0 is in LDS
-#if defined(TTK_R_STAMP)
-  TTK_STAMP(st_loop0);
-  st_wait = 0;
-#endif
+  rbarrier();  // stage 0 is in LDS
 
   // One k32 step: MFMAs on stage `it` (ring slot PAR = it & 1) with, when CONV, the conversion of stage it + 1 (register set and ring
   // slot PAR ^ 1) between them; then the rows of stage it + 3 are requested into the set just freed.  Vector-memory order of a step:
@@ -840,97 +614,36 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
     if constexpr (CONV) {
       dma_b(it + 1, PAR ^ 1);  // that slot was released by the barrier just passed
       conv_ks = it + 1;
-      if constexpr (FWD) conv_consts(it + 1);
     }
-    if constexpr (M16) {
-      // hold the B fragments of the step (2 TN blocks x 2 pieces), stream the A fragments one 16-row block ahead
-      f16x8 hb[2 * TN][2], sa16[2][2];
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int j = 0; j < 2 * TN; ++j) hb[j][p] = rd(S0, BPL, b16_off[j], p);
-        sa16[0][p] = rd(S0, APL, a16_off[0], p);
-      }
-      static_for<2 * TM>([&](auto ic) {
-        constexpr int i = decltype(ic)::value, cur = i & 1;
-        if constexpr (i + 1 < 2 * TM) {
-#pragma unroll
-          for (int p = 0; p < 2; ++p) sa16[cur ^ 1][p] = rd(S0, APL, a16_off[i + 1], p);
-        }
-        const bool blk_live = i * 16 < live_rows16;  // (uniform) a 16-row block wholly behind the end of the row block holds zeros: no products
-        static_for<2 * TN>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
-          if constexpr (kRDbg & 4) {
-            asm volatile("" ::"v"(sa16[cur][0]), "v"(hb[j][0]));
-          } else {
-            if (blk_live) {
-              acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa16[cur][0], hb[j][1], acc16[i][j], 0, 0, 0);
-              acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa16[cur][1], hb[j][0], acc16[i][j], 0, 0, 0);
-              acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa16[cur][0], hb[j][0], acc16[i][j], 0, 0, 0);
-            }
-          }
-          constexpr int q = i * (2 * TN) + j;  // MFMA triple of the step: 4 RBLK of them, a conversion part behind every fourth
-          if constexpr (CONV && (q & 3) == 3) {
-            conv_part(SN{}, SN{}, std::integral_constant<int, (q >> 2)>{});
-#if TTK_M_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-          }
-        });
-      });
-    } else {
+    // hold the B fragments of the step (2 TN blocks x 2 pieces), stream the A fragments one 16-row block ahead
+    f16x8 hb[2 * TN][2], sa16[2][2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
 #pragma unroll
-      for (int y = 0; y < TH; ++y) hold[y][p] = rd(S0, HPL, hold_off[y], p);
-      strm[0][p] = rd(S0, SPL, strm_off[0], p);
+      for (int j = 0; j < 2 * TN; ++j) hb[j][p] = rd(S0, BPL, b16_off[j], p);
+      sa16[0][p] = rd(S0, APL, a16_off[0], p);
     }
-    // software pipeline of the fragment reads as in pw16r_k: the stream fragment of block x + 1 is requested before the MFMAs of
-    // block x, the hold fragments of the second k16 stage replace the first's behind their last use
-    static_for<2>([&](auto subc) {
-      constexpr int sub = decltype(subc)::value;
-      const unsigned char* S = S0 + sub * kStr;
-      static_for<TS>([&](auto xc) {
-        constexpr int x = decltype(xc)::value;
-        constexpr int cur = (sub * TS + x) & 1;
-        constexpr bool last = x + 1 == TS;
-        if constexpr (!last) {
+    static_for<2 * TM>([&](auto ic) {
+      constexpr int i = decltype(ic)::value, cur = i & 1;
+      if constexpr (i + 1 < 2 * TM) {
 #pragma unroll
-          for (int p = 0; p < 2; ++p) strm[cur ^ 1][p] = rd(S, SPL, strm_off[x + 1], p);
-        } else if constexpr (sub == 0) {
-#pragma unroll
-          for (int p = 0; p < 2; ++p) strm[cur ^ 1][p] = rd(S + kStr, SPL, strm_off[0], p);
+        for (int p = 0; p < 2; ++p) sa16[cur ^ 1][p] = rd(S0, APL, a16_off[i + 1], p);
+      }
+      const bool blk_live = i * 16 < live_rows16;  // (uniform) a 16-row block wholly behind the end of the row block holds zeros: no products
+      static_for<2 * TN>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        if (blk_live) {  // three piece products of one accumulator, smallest first: h_a l_b, l_a h_b, h_a h_b
+          acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa16[cur][0], hb[j][1], acc16[i][j], 0, 0, 0);
+          acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa16[cur][1], hb[j][0], acc16[i][j], 0, 0, 0);
+          acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa16[cur][0], hb[j][0], acc16[i][j], 0, 0, 0);
         }
-        static_for<TH>([&](auto yc) {
-          constexpr int y = decltype(yc)::value;
-          // three piece products of one accumulator, smallest first: h_a l_b, l_a h_b, h_a h_b
-          if constexpr (HOLD_A) {
-            acc[y][x] = rmfma(hold[y][0], strm[cur][1], acc[y][x]);
-            acc[y][x] = rmfma(hold[y][1], strm[cur][0], acc[y][x]);
-            acc[y][x] = rmfma(hold[y][0], strm[cur][0], acc[y][x]);
-          } else {
-            acc[x][y] = rmfma(strm[cur][0], hold[y][1], acc[x][y]);
-            acc[x][y] = rmfma(strm[cur][1], hold[y][0], acc[x][y]);
-            acc[x][y] = rmfma(strm[cur][0], hold[y][0], acc[x][y]);
-          }
-          if constexpr (last && sub == 0) {  // hold fragment y of the second k16 stage, behind its last use in the first
-#pragma unroll
-            for (int p = 0; p < 2; ++p) hold[y][p] = rd(S + kStr, HPL, hold_off[y], p);
-          }
-          constexpr int q = (sub * TS + x) * TH + y;  // MFMA triple of the step
-          if constexpr (CONV && (q & 1) == 1) {
-            conv_part(SN{}, SN{}, std::integral_constant<int, (q >> 1)>{});
-#if TTK_M_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-          }
-        });
+        constexpr int q = i * (2 * TN) + j;  // MFMA triple of the step: 4 RBLK of them, a conversion part behind every fourth
+        if constexpr (CONV && (q & 3) == 3) {
+          conv_part(SN{}, SN{}, std::integral_constant<int, (q >> 2)>{});
+          __builtin_amdgcn_sched_barrier(0);  // a scheduling fence behind every conversion part
+        }
       });
     });
-    }
-#if defined(TTK_R_STAMP)
-    TTK_STAMP(st_x);
-#endif
     if constexpr (CONV) {
       if (it + 3 < nks) {
         load_a(it + 3, SN{});
@@ -939,11 +652,7 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
-#if defined(TTK_R_STAMP)
-    TTK_STAMP(st_y);
-    st_aux += st_y - st_x;
-#endif
-    TTK_RB();  // done with stage `it` (its fragments are in registers, its slot may be refilled); stage it + 1 is in LDS
+    rbarrier();  // done with stage `it` (its fragments are in registers, its slot may be refilled); stage it + 1 is in LDS
   };
   // (one loop body of two converting steps and a tail: with the step variants inside the loop hipcc kept two copies of the accumulators)
   int it = 0;
@@ -957,28 +666,7 @@ __global__ void __launch_bounds__(512) pw16m_k(const float* __restrict__ A0, con
   } else {
     step(it, P0{}, P0{});
   }
-#if defined(TTK_R_STAMP)
-  TTK_STAMP(st_loop1);
-#endif
-#undef TTK_RB
-  if constexpr (M16) r_epilogue<RBLK, MODE, 8, decltype(acc16), true>(lds, acc16, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
-  else r_epilogue<RBLK, MODE, 8>(lds, acc, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
-#if defined(TTK_R_STAMP)
-  {
-    unsigned long long st_t1, st_r1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TTK_STAMP(st_t1);
-    TTK_RSTAMP(st_r1);
-    if ((tid & 63) == 0 && blockIdx.x < 2048) {
-      unsigned long long* d = g_r_stamps + ((size_t)blockIdx.x * 12 + wave) * 8;
-      d[0] = st_loop0 - st_t0; d[1] = st_loop1 - st_loop0; d[2] = st_t1 - st_loop1; d[3] = st_wait; d[4] = st_aux; d[5] = st_r1 - st_r0; d[6] = st_t1 - st_t0;
-      d[7] = st_r0;
-      if (wave == 0)  // (the stamp reader expects twelve waves: rows 8..11 repeat wave 0)
-        for (int w = 8; w < 12; ++w)
-          for (int i = 0; i < 8; ++i) g_r_stamps[((size_t)blockIdx.x * 12 + w) * 8 + i] = d[i];
-    }
-  }
-#endif
+  r_epilogue<RBLK, RMODE_DGRAD, 8, decltype(acc16), true>(lds, acc16, out, E0, bnE, part, M, Nout, m0, m_end, n0, by, sa, sb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1299,18 +987,21 @@ bool launch_f16r_gemm(const float* A0, const float* A1, const float* bnA, const 
   const RPlan pl = r_plan(M, K, Nout);
   const unsigned tiles = (unsigned)pl.row_blocks * (Nout / kRBN);
 #define TTK_M_LAUNCH(RBLK_) \
-  hipLaunchKernelGGL((pw16m_k<RBLK_, MODE, (TTK_M_M16 != 0)>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
+  hipLaunchKernelGGL((pw16m_k<RBLK_>), dim3(tiles), dim3(512), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
 #define TTK_R_LAUNCH(RBLK_) \
   hipLaunchKernelGGL((pw16r_k<RBLK_, MODE>), dim3(tiles), dim3(768), 0, st, A0, A1, bnA, Bq, wmax, out, E0, bnE, part, M, K, Nout, pl.rt)
   // Which form runs what, from same-box runs of the whole step (profiles/r04_rowblock_gemm_variants.txt): the eight-wave form takes the
   // data gradient (two tensors to convert per element: 0.617 vs 0.644 ms per step), the twelve-wave form keeps the forward (0.478 vs
   // 0.485) and the 256-row tiles (128 accumulator registers + two sets of rows do not fit the eight-wave form's 256).
-  const bool merged = TTK_R_MERGED == 2 || (TTK_R_MERGED == 1 && MODE == RMODE_DGRAD);
-  if (merged && pl.rblk == 4) TTK_M_LAUNCH(4);
-  else if (merged && pl.rblk == 6) TTK_M_LAUNCH(6);
-  else if (pl.rblk == 4) TTK_R_LAUNCH(4);
-  else if (pl.rblk == 6) TTK_R_LAUNCH(6);
-  else TTK_R_LAUNCH(8);
+  if constexpr (MODE == RMODE_DGRAD) {
+    if (pl.rblk == 4) TTK_M_LAUNCH(4);
+    else if (pl.rblk == 6) TTK_M_LAUNCH(6);
+    else TTK_R_LAUNCH(8);
+  } else {
+    if (pl.rblk == 4) TTK_R_LAUNCH(4);
+    else if (pl.rblk == 6) TTK_R_LAUNCH(6);
+    else TTK_R_LAUNCH(8);
+  }
 #undef TTK_R_LAUNCH
 #undef TTK_M_LAUNCH
   return true;
@@ -1322,13 +1013,3 @@ template bool launch_f16r_gemm<RMODE_DGRAD>(const float*, const float*, const fl
                                             int, int, void*, float*, hipStream_t);
 
 }  // namespace ttk
-
-#if defined(TTK_R_STAMP)
-extern "C" int ttk_debug_read_r_stamps(void* host_dst, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ttk::g_r_stamps), bytes < sizeof(ttk::g_r_stamps) ? bytes : sizeof(ttk::g_r_stamps));
-}
-#endif
-
-#if TTK_M_NOPK && defined(__HIP_DEVICE_COMPILE__)
-#pragma clang attribute pop
-#endif

@@ -38,7 +38,8 @@ __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + 
 // The library reads exactly one environment variable, TTK_DETERMINISTIC (a documented mode: DESIGN.md 4.8).  The A/B switches of earlier
 // rounds (kernel selection, forced tilings: TTK_GEMM, TTK_GEMM_R, TTK_R_RBLK, TTK_R_ALL, TTK_WGRAD_T, TTK_STEM, TTK_STEM7_VALU,
 // TTK_FUSED_FP32, TTK_FUSED_WIDE, TTK_CONV_WIDE64, TTK_DW_COLTILE) existed in experiment builds up to commit 84e21f6 and went with the
-// kernels that lost their measurements (profiles/exp_switches_codegen.txt); what remains for A/B builds are compile-time -D parameters.
+// kernels that lost their measurements (profiles/exp_switches_codegen.txt).  The compile-time -D parameters, timing-only bit masks and
+// cycle stamps of the kernel sources existed up to commit 455eb54 (profiles/compile_switches_codegen.txt): the sources have no switches.
 inline bool deterministic_mode() {
   static const bool det = [] { const char* e = getenv("TTK_DETERMINISTIC"); return e && e[0] != '0'; }();
   return det;

@@ -48,6 +48,21 @@ def test_library_has_no_kernel_selection_switches():
                     assert word not in text, f"{word} in {os.path.join(d, f)}"
 
 
+def test_kernel_sources_have_no_compile_time_switches():
+    """No preprocessor conditional of csrc/ names a TTK_ macro: the sources have one form, the one the product is built from (the
+    conditionals that remain test __HIPCC__, __clang__ and __HIP_DEVICE_COMPILE__)."""
+    import glob
+    import re
+
+    csrc = os.path.join(PKG, "csrc")
+    sources = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(sources) > 30
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b")
+    lines = [(os.path.basename(p), n + 1, line) for p in sources for n, line in enumerate(open(p).read().split("\n")) if cond.match(line)]
+    assert lines  # (the compiler-macro conditionals: the scan does see conditionals)
+    assert [x for x in lines if "TTK_" in x[2]] == []
+
+
 @pytest.mark.parametrize("unc,pt", [(True, True), (False, True), (False, False)])
 def test_state_dict_inventory(unc, pt):
     from trackertraincode.neuralnets.models import NetworkWithPointHead

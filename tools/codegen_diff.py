@@ -7,8 +7,10 @@ Every neuralnet-tracker-traincode_amd/csrc/*.hip of either tree is compiled devi
 (FLAGS, plus the per-file FLAGS_<name>):   hipcc <flags> --cuda-device-only -S FILE -o OUT.s
 From the assembly each kernel (every .amdhsa_kernel symbol) is cut out - from its label to .Lfunc_end: the body and the kernel descriptor -
 and normalised: __hip_cuid_ lines dropped, local labels (.LBBn_m, .Ltmpn, .Lfunc_endn and the BBn_m of the loop comments, all of which
-count the functions in front of the kernel) renumbered in order of appearance.  Kernels are paired by demangled name and compared as text.
-The method of profiles/gemm_family_cleanup_codegen.txt, fp32_storage_params_codegen.txt and exp_switches_codegen.txt.
+count the functions in front of the kernel) renumbered in order of appearance, the blanks between a block label and its loop comment (padded
+to a fixed column, so they count the digits of the function number) reduced to one.  Kernels are paired by demangled name and compared as text.
+The method of profiles/gemm_family_cleanup_codegen.txt, fp32_storage_params_codegen.txt, exp_switches_codegen.txt and
+compile_switches_codegen.txt.
 """
 import argparse
 import concurrent.futures
@@ -42,6 +44,8 @@ def compile_s(args):
 
 LABEL = re.compile(r"\.LBB\d+_\d+|\.Ltmp\d+|\.Lfunc_end\d+|\.Lfunc_begin\d+|\bBB\d+_\d+")
 
+LABEL_PAD = re.compile(r"^(\.LBB\d+_\d+:) +;")
+
 
 def normalise(lines):
     seen = {}
@@ -53,7 +57,8 @@ def normalise(lines):
             seen[t] = f"{kind}#{sum(1 for k in seen if k.startswith(kind))}"
         return seen[t]
 
-    return [LABEL.sub(sub, ln.rstrip()) for ln in lines if "__hip_cuid_" not in ln]
+    # (a block label's loop comment is padded to a fixed column, so its blanks count the digits of the function number too)
+    return [LABEL.sub(sub, LABEL_PAD.sub(r"\1 ;", ln.rstrip())) for ln in lines if "__hip_cuid_" not in ln]
 
 
 def kernels_of(path):

@@ -32,13 +32,6 @@ crit, _ = S.setup_losses(script_args(meta["flags"]), net)
 batches = make_batches(meta, "cuda")
 state0 = {k: v.detach().clone() for k, v in net.state_dict().items()}
 names, sums = [], []
-import ctypes
-import trackertraincode._hip as H
-dump = None
-if hasattr(H.lib().cdll, "ttk_debug_set_heads_dump"):  # a -DTTK_HEADS_DBG build (TTK_LIB=...): per-lane intermediates of heads_fwd_k
-    dump = torch.zeros(B, 64, 16, device="cuda")
-    H.lib().cdll.ttk_debug_set_heads_dump.argtypes = [ctypes.c_void_p]
-    assert H.lib().cdll.ttk_debug_set_heads_dump(dump.data_ptr()) == 0
 def cs(name, t):
     if torch.is_tensor(t) and t.is_floating_point():
         names.append(name); sums.append(torch.stack([t.double().sum(), t.double().abs().sum()]))
@@ -48,7 +41,6 @@ def walk(name, o):
         cs(name, o)
         if name == "fwd:net.pt3d_68":
             keep["pts"] = o.detach().clone()
-            if dump is not None: keep["dump"] = dump.clone()
     elif isinstance(o, dict):
         for k, v in o.items(): walk(f"{name}.{k}", v)
     elif isinstance(o, (list, tuple)):
@@ -74,7 +66,6 @@ for it in range(N):
     if ref is None:
         ref = cur
         keep["ref"] = keep["pts"]
-        keep["dref"] = keep.get("dump")
         continue
     assert cur[0] == ref[0]
     d = (cur[1][:, 0] - ref[1][:, 0]).abs() / ref[1][:, 1].clamp_min(1e-30)
@@ -84,13 +75,6 @@ for it in range(N):
         dd = (keep["pts"] != keep["ref"])
         w = dd.nonzero()
         print(f"   pt3d_68: {len(w)} elements differ, samples {sorted(set(w[:, 0].tolist()))[:10]}, points {sorted(set(w[:, 1].tolist()))[:70]}; e.g. {keep['pts'][dd][:6].tolist()} vs {keep['ref'][dd][:6].tolist()}")
-        if dump is not None:
-            dm = (keep["dump"] != keep["dref"])
-            wd = dm.nonzero()
-            cols = sorted(set(wd[:, 2].tolist()))
-            print(f"   dump: {len(wd)} entries differ; lanes {sorted(set(wd[:, 1].tolist()))}; columns {cols} (0-2 local, 3-6 qk, 7-9 ck, 10-11 sh, 12 kp, 13 eig, 14-15 out)")
-            for (ss, ll, cc) in wd[:6].tolist():
-                print(f"      sample {ss} lane {ll} col {cc}: {keep['dump'][ss, ll, cc].item():.7g} vs {keep['dref'][ss, ll, cc].item():.7g}")
         other = [cur[0][i] for i in idx if not (cur[0][i].startswith("grad:convnet") or (cur[0][i][0] == "g" and cur[0][i][1:].isdigit()))]
         print(f"   outside the backbone: {other[:12]}")
         print(f"iteration {it}: {len(idx)} checksums differ; first: " + "; ".join(f"{cur[0][i]} ({d[i]:.2e})" for i in idx[:6]), flush=True)

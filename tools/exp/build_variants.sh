@@ -1,6 +1,8 @@
 #!/bin/bash
-# Experiment builds of libttk_hip.so: one translation unit recompiled with -D flags, linked with the product's other objects.
-#   bash tools/exp/build_variants.sh <name> <source.hip> "<-D flags>" [<name> <source.hip> "<flags>" ...]
+# Experiment builds of libttk_hip.so: one translation unit recompiled with flags of its own, linked with the product's other objects.
+# The kernel sources have no -D switches: a variant is another compiler flag (-save-temps, -mllvm ...) or an edited copy of the source
+# beside the original in csrc/ (<source.hip> is taken relative to csrc/).
+#   bash tools/exp/build_variants.sh <name> <source.hip> "<flags>" [<name> <source.hip> "<flags>" ...]
 # -> tools/exp/_build/libttk_<name>.so   (select with TTK_LIB=...; never shipped, never loaded by the product)
 set -e
 R=$(cd "$(dirname "$0")/../.." && pwd)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Register / LDS / spill summary of every kernel of one translation unit:  bash tools/exp/kernel_regs.sh pwconv_r.hip [-D flags] [filter]
+# Register / LDS / spill summary of every kernel of one translation unit:  bash tools/exp/kernel_regs.sh pwconv_r.hip [compiler flags]
 R=$(cd "$(dirname "$0")/../.." && pwd); C=$R/neuralnet-tracker-traincode_amd/csrc
 src=$1; shift
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only -I$R/include "$@" -o /tmp/kregs_$$.s $C/$src 2>/dev/null
