@@ -54,7 +54,7 @@ extern "C" {
 
 typedef void* ttk_stream_t; /* hipStream_t */
 
-#define TTK_ABI_VERSION 37
+#define TTK_ABI_VERSION 38
 
 /* rows of a layer's BatchNorm constant block  float bn[TTK_BN_ROWS][C] */
 enum {
@@ -899,6 +899,44 @@ int ttk_track_crop(const void* frames, int src_is_u8, int S, int T, int Hs, int 
 int ttk_track_update(const float* roi, const float* coord, const float* pose, const float* pts, const float* tr, int* t_dev, int L, int N,
                      int T, int Hs, int Ws, const float* lane_factor, float* roi_state, float* traj_roi_in, float* traj_roi,
                      float* traj_coord, float* traj_pose, float* traj_pts, unsigned char* lost, ttk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (ABI 38) Fit of the deformable face model to 68 landmarks (csrc/facefit.hip, csrc/facefit_math.h; reference
+ * scripts/DsWflwFitFaceModel.ipynb / DsLapaMegafaceFitFaceModel.ipynb, class DeformableHeadFitting, which fits one sample at a time on
+ * the CPU with two BFGS runs of the third-party torchmin).  Per sample the unknowns are x[57] = (q[4] in i,j,k,w order, c[3] = x, y, size,
+ * s[50]), everything in the crop's normalised [-1, 1] coordinates, and with qh = q / |q|, P = rigid_transformation_25d(qh, c[:2], c[2],
+ * keypts + sum_i s_i keyeigvecs_i) the objective is the reference's `lossfunc`:
+ *     f(x) = (1/136) sum_p sum_{d in x,y} weight_p huber_0.1(P_pd - target_pd) + 1e-6 (1 - |q|)^2
+ *            + 0.01 * (-(1/150) log p_GMM(s)) + 10 exp(-c[2] / 0.05)
+ * huber_b(r) = r^2 / (2 b) for |r| < b, else |r| - b / 2 (smooth_l1_loss).  ck[K], mu[K][50], sinv[K][50] are the mixture's float64
+ * constants as ttk_loss_gmm_fwd takes them (ck = log w_k + sum_d log sinv_kd - 25 log 2 pi), 1 <= K <= 16.  keypts[68][3] and
+ * keyeigvecs[50][68][3] are float32; x, target[B][68][2] and weight[B][68] are float32 and widened on load; every sum, the optimiser's
+ * state and the point math are float64.  One workgroup per sample; no atomics: two runs are bitwise equal.
+ *   ttk_facefit_objective  f[B] and g[B][57] = df/dx at x[B][57], by the device function the optimiser calls.  n_free = 7 frees the pose
+ *                          only (g[7:] is written as 0), n_free = 57 everything.
+ *   ttk_facefit            the project's own two-stage BFGS (a deliberate deviation: torchmin's iterates cannot be pinned without the
+ *                          package).  Stage 1 frees x[0:7] for at most iters1 iterations until |g|_inf <= gtol1, stage 2 all 57 for at
+ *                          most iters2 until |g|_inf <= gtol2, whatever stage 1's status was.  Per stage the inverse Hessian H starts at
+ *                          I.  An iteration: d = -H g (g.d >= 0: H = I, d = -g); t = 1, on the first iteration of a stage
+ *                          min(1, 1 / |g|_1); t is halved at most 30 times until f(x + t d) is finite and <= f + 1e-4 t g.d - no step
+ *                          accepted ends the stage with status 2 and x unchanged; with s = t d, y = g_new - g, H takes the BFGS inverse
+ *                          update only if s.y > 1e-10 |s| |y|.  The convergence test runs before every iteration and after the last.
+ *                          x_out[B][57]      the final x with the quaternion normalised;
+ *                          pts_out[B][68][3] P at the final x;
+ *                          f_out[B][2]       f at x0 and at the final x;
+ *                          status[B]         stage 2's: 0 converged, 1 iteration limit, 2 line search, 3 = a non-finite value in the
+ *                                            sample's x0, target or weight, or a non-finite f(x0): no iteration, x_out = x0 as given;
+ *                          iters[B][2]       iterations of stage 1 and stage 2.
+ *                          Every loop of the kernel has an integer bound: no input, NaN and Inf included, can keep a workgroup running.
+ * Both: no allocation, no synchronisation, one launch.  -1 before anything is launched or written for a null pointer, K outside [1, 16],
+ * n_free outside {7, 57}, a negative iteration limit, a gtol that is not positive, B < 0; B = 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int ttk_facefit_objective(const float* x, const float* target, const float* weight, const float* keypts, const float* keyeigvecs,
+                          const double* ck, const double* mu, const double* sinv, int K, int B, int n_free, double* f, double* g,
+                          ttk_stream_t stream);
+int ttk_facefit(const float* x0, const float* target, const float* weight, const float* keypts, const float* keyeigvecs, const double* ck,
+                const double* mu, const double* sinv, int K, int B, int iters1, double gtol1, int iters2, double gtol2, float* x_out,
+                float* pts_out, double* f_out, int* status, int* iters, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Streaming probe (measurement infrastructure: bench.py `copy_probe`, tools/stream_sweep.py; no reference counterpart).

@@ -105,6 +105,8 @@ _SIGNATURES = {
     "ttk_ensemble_reduce": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "ttk_track_crop": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P],
     "ttk_track_update": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ttk_facefit_objective": [_P] * 8 + [_I, _I, _I, _P, _P],
+    "ttk_facefit": [_P] * 8 + [_I, _I, _I, _D, _I, _D, _P, _P, _P, _P, _P],
     "ttk_intensity_augment": [_P, _P, _P, _P, _I, _I, _I, _F],
     "ttk_clip_adam": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P],
     "ttk_clip_adam_guarded": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P],
@@ -133,7 +135,7 @@ _SIGNATURES = {
     "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
 }
 
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 ADAM_HEALTH_SKIPPED, ADAM_HEALTH_CONSECUTIVE, ADAM_HEALTH_CULPRIT, ADAM_HEALTH_WORDS = 0, 1, 2, 4  # TTK_ADAM_HEALTH_*
 

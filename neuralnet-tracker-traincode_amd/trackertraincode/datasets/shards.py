@@ -42,24 +42,9 @@ def _decode_grey(blob: bytes) -> np.ndarray:
     return np.asarray(Image.open(io.BytesIO(blob)).convert("L"), dtype=np.uint8)
 
 
-def decode_pose_shard(path: str, half_pixel_offset: bool = True) -> dict:
-    """{"image": uint8 [N,1,H,W] (zero-padded to the largest frame), "image_size": int32 [N,2] (w, h), labels...}"""
-    d = np.load(path)
-    if "image_bytes" in d.files:
-        lengths = d["image_lengths"].astype(np.int64)
-        offs = np.concatenate([[0], np.cumsum(lengths)])
-        blob = d["image_bytes"]
-        frames = [_decode_grey(blob[offs[i]:offs[i + 1]].tobytes()) for i in range(len(lengths))]
-    elif "images" in d.files:
-        imgs = d["images"]
-        frames = [_to_grey(im) for im in imgs]
-    else:
-        raise ValueError(f"{path}: neither image_bytes/image_lengths nor images")
-    H, W = max(f.shape[0] for f in frames), max(f.shape[1] for f in frames)
-    image = np.zeros((len(frames), 1, H, W), np.uint8)
-    for i, f in enumerate(frames):
-        image[i, 0, :f.shape[0], :f.shape[1]] = f
-    out = {"image": image, "image_size": np.array([[f.shape[1], f.shape[0]] for f in frames], np.int32)}
+def _decode_labels(d, half_pixel_offset: bool) -> dict:
+    """The label arrays of an opened shard under their Batch names, with the half-pixel offset: decode_pose_shard without the images."""
+    out = {}
     for src, dst in _NAME_MAP.items():
         if src in d.files:
             v = np.asarray(d[src])
@@ -78,8 +63,43 @@ def decode_pose_shard(path: str, half_pixel_offset: bool = True) -> dict:
             if k in out:
                 out[k] = out[k].copy()
                 out[k][..., :2] += 0.5
+    return out
+
+
+def decode_pose_shard(path: str, half_pixel_offset: bool = True) -> dict:
+    """{"image": uint8 [N,1,H,W] (zero-padded to the largest frame), "image_size": int32 [N,2] (w, h), labels...}"""
+    d = np.load(path)
+    if "image_bytes" in d.files:
+        lengths = d["image_lengths"].astype(np.int64)
+        offs = np.concatenate([[0], np.cumsum(lengths)])
+        blob = d["image_bytes"]
+        frames = [_decode_grey(blob[offs[i]:offs[i + 1]].tobytes()) for i in range(len(lengths))]
+    elif "images" in d.files:
+        imgs = d["images"]
+        frames = [_to_grey(im) for im in imgs]
+    else:
+        raise ValueError(f"{path}: neither image_bytes/image_lengths nor images")
+    H, W = max(f.shape[0] for f in frames), max(f.shape[1] for f in frames)
+    image = np.zeros((len(frames), 1, H, W), np.uint8)
+    for i, f in enumerate(frames):
+        image[i, 0, :f.shape[0], :f.shape[1]] = f
+    out = {"image": image, "image_size": np.array([[f.shape[1], f.shape[0]] for f in frames], np.int32)}
+    out.update(_decode_labels(d, half_pixel_offset))
     n = {len(v) for v in out.values()}
     if len(n) != 1:
+        raise ValueError(f"{path}: fields of different lengths")
+    return out
+
+
+def read_labels(path: str, half_pixel_offset: bool = True) -> dict:
+    """The labels of a shard as decode_pose_shard returns them (names mapped, float32, `individual`, half-pixel offset) without decoding
+    one image: what a tool that only re-labels a shard needs (scripts/fit_face_model.py)."""
+    with np.load(path) as d:
+        if "image_lengths" not in d.files and "images" not in d.files:
+            raise ValueError(f"{path}: neither image_bytes/image_lengths nor images")
+        out = _decode_labels(d, half_pixel_offset)
+    n = {len(v) for v in out.values()}
+    if len(n) > 1:
         raise ValueError(f"{path}: fields of different lengths")
     return out
 
@@ -96,6 +116,7 @@ def load_resident_frames(path: str, tag, device="cuda", coord_convention_id: int
 # ---------------------------------------------------------------------------------------------
 _LABEL_ARRAYS = {"pose": "quats", "coord": "coords", "pt3d_68": "pt3d_68", "shapeparam": "shapeparams"}  # Batch name -> HDF5 name
 _STAT_ARRAYS = {"rot_spread": "pseudolabel_rot_spread", "mean_quat_norm": "pseudolabel_mean_quat_norm", "coord_spread": "pseudolabel_coord_spread"}
+_FIT_ARRAYS = {"objective": "facefit_objective", "status": "facefit_status", "iterations": "facefit_iterations"}  # face-model fit
 
 
 def write_pseudolabels(src: str, dst: str, labels: dict, keep=None, overwrite: bool = False) -> str:
@@ -109,15 +130,29 @@ def write_pseudolabels(src: str, dst: str, labels: dict, keep=None, overwrite: b
     `keep`: boolean frame mask; dropped frames leave every per-frame array (the reference's filter_dataset.filter_file_by_frames) - like
     it, a shard with `sequence_starts` is refused when frames are dropped.  Label arrays the shard already has, and an existing `dst`,
     are replaced only with overwrite=True.  The write goes to a temporary file next to `dst`, then os.replace: no partial shard."""
+    return _rewrite_labels(src, dst, labels, _STAT_ARRAYS, ("pose", "coord"), ".pseudolabels-", keep, overwrite)
+
+
+def write_face_fit(src: str, dst: str, labels: dict, keep=None, overwrite: bool = False) -> str:
+    """The shard `src` with the labels of a face-model fit (facemodel.fitting.FaceModelFitter.fit) written to `dst`: write_pseudolabels'
+    machinery - the same half-pixel rule, `keep`, temporary file + os.replace and refusals - for "pose" [N,4], "coord" [N,3], "pt3d_68"
+    [N,68,3] and "shapeparam" [N,50] (all four required: they are what the fit is run for), stored as quats, coords, pt3d_68, shapeparams,
+    and optionally "objective" [N], "status" [N], "iterations" [N,2], stored as facefit_objective (float32), facefit_status and
+    facefit_iterations (int32), which decode_pose_shard does not read."""
+    return _rewrite_labels(src, dst, labels, _FIT_ARRAYS, ("pose", "coord", "pt3d_68", "shapeparam"), ".facefit-", keep, overwrite)
+
+
+def _rewrite_labels(src, dst, labels, extra_arrays, required, tmp_prefix, keep, overwrite) -> str:
     import os
     import tempfile
 
     def host(v):
         return np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v)
 
-    unknown = set(labels) - set(_LABEL_ARRAYS) - set(_STAT_ARRAYS)
-    if unknown or "pose" not in labels or "coord" not in labels:
-        raise ValueError(f"labels need 'pose' and 'coord' and may hold {sorted(set(_LABEL_ARRAYS) | set(_STAT_ARRAYS))}; got {sorted(labels)}")
+    unknown = set(labels) - set(_LABEL_ARRAYS) - set(extra_arrays)
+    if unknown or any(k not in labels for k in required):
+        need = " and ".join(repr(k) for k in required) if len(required) == 2 else ", ".join(repr(k) for k in required)
+        raise ValueError(f"labels need {need} and may hold {sorted(set(_LABEL_ARRAYS) | set(extra_arrays))}; got {sorted(labels)}")
     with np.load(src) as d:
         arrays = {k: d[k] for k in d.files}
     if "image_lengths" in arrays:
@@ -128,13 +163,14 @@ def write_pseudolabels(src: str, dst: str, labels: dict, keep=None, overwrite: b
         raise ValueError(f"{src}: neither image_bytes/image_lengths nor images")
     new = {}
     for k, v in labels.items():
-        v = host(v).astype(np.float32)
+        v = host(v)
+        v = v.astype(np.int32) if k in ("status", "iterations") else v.astype(np.float32)
         if len(v) != n:
             raise ValueError(f"labels[{k!r}] has {len(v)} rows, {src} has {n} frames")
         if k in ("coord", "pt3d_68"):
             v = v.copy()
             v[..., :2] -= np.float32(0.5)
-        new[_LABEL_ARRAYS.get(k) or _STAT_ARRAYS[k]] = v
+        new[_LABEL_ARRAYS.get(k) or extra_arrays[k]] = v
     present = sorted(set(new) & set(arrays))
     if not overwrite and (present or os.path.exists(dst)):
         raise FileExistsError((f"{dst} exists" if os.path.exists(dst) else f"{src} already has {present}") + ": pass overwrite=True to replace")
@@ -155,7 +191,7 @@ def write_pseudolabels(src: str, dst: str, labels: dict, keep=None, overwrite: b
         arrays = {k: (v[keep] if v.ndim >= 1 and len(v) == n else v) for k, v in arrays.items()}
         if "image_lengths" in arrays:
             arrays["image_bytes"] = kept_blob
-    fd, tmp = tempfile.mkstemp(dir=os.path.dirname(os.path.abspath(dst)), prefix=".pseudolabels-", suffix=".npz")
+    fd, tmp = tempfile.mkstemp(dir=os.path.dirname(os.path.abspath(dst)), prefix=tmp_prefix, suffix=".npz")
     try:
         with os.fdopen(fd, "wb") as f:
             np.savez(f, **arrays)
