@@ -458,7 +458,8 @@ def blocked_sum(P, T):
 
 
 def serial_sum(T):
-    acc = np.zeros((9, T.shape[2]), np.float32)
+    """T[taps][pixels][ch] -> [taps][ch]: one float32 chain per tap over the pixels in order"""
+    acc = np.zeros((T.shape[0], T.shape[2]), np.float32)
     for p in range(T.shape[1]):
         acc = (acc + T[:, p]).astype(np.float32)
     return acc
@@ -485,15 +486,20 @@ def wgrad(case):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # statistics
 # ---------------------------------------------------------------------------------------------------------------------------------
-def stat_ratios(part, v, d, square):
+def stat_ratios(part, v, d, square, length=None):
     """part[rows][2][C] against the stored tensors: row 0 = sum v (forward: v = y - pivot; backward: v = g_prev), row 1 = sum v * d
     (forward, square: d = v, the bound 2 U sum v^2; backward: d = yprev - mean, the bound U sum |v d|), each plus U sum_rows |part_row|.
+    length: the kernel sums in float32 and no term passes through more than `length` additions (tests/anyc_ref.py derives it): the bound
+    is then length U sum |v| and (length + 2) U sum |v d|.
     v, d: [pixels][C] float64.  Returns the worst |error| / bound of either row (0 / 0 = 0)."""
     ps = np.asarray(part, np.float64)
     out = []
     for k, terms in ((0, v), (1, v * d)):
         err = np.abs(ps[:, k].sum(0) - terms.sum(0))
-        bound = (2.0 if (k == 1 and square) else 1.0) * U * np.abs(terms).sum(0) + U * np.abs(ps[:, k]).sum(0)
+        if length is None:
+            bound = (2.0 if (k == 1 and square) else 1.0) * U * np.abs(terms).sum(0) + U * np.abs(ps[:, k]).sum(0)
+        else:
+            bound = (length + 2.0 * k) * U * np.abs(terms).sum(0)
         with np.errstate(divide="ignore", invalid="ignore"):
             out.append(float(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf)).max()))
     return out

@@ -281,8 +281,10 @@ def cases_of(letter):
 # inputs
 # ---------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=4)
-def make_case(case):
-    """The float32 inputs of one case (never written afterwards) and the exact operand `a` with its term bound."""
+def make_case(case, zero_channels=None, closed_channel=None):
+    """The float32 inputs of one case (never written afterwards) and the exact operand `a` with its term bound.  zero_channels (a tuple),
+    closed_channel: where the planted channels go (tests/anyc_ref.py puts one into the narrow last channel block); None: the tuned
+    family's places."""
     M, Cin, Cout = case
     rng = np.random.default_rng(1000003 * M + 1009 * Cin + Cout)
     c = types.SimpleNamespace(case=case, M=M, Cin=Cin, Cout=Cout)
@@ -290,7 +292,8 @@ def make_case(case):
     c.w = (rng.normal(0, 1, (Cout, Cin)) * np.sqrt(2.0 / Cout)).astype(np.float32)
     c.piv = rng.normal(0, 0.5, Cout).astype(np.float32)
     c.bn_dw, c.bn = bn_block(Cin, rng), bn_block(Cout, rng)  # c.bn: the pointwise layer's own block (conv_ref.dy_terms reads it)
-    c.zero_channels, c.closed_channel = [1, Cin // 2 + 3], Cin // 4 + 2
+    c.zero_channels = [1, Cin // 2 + 3] if zero_channels is None else list(zero_channels)
+    c.closed_channel = Cin // 4 + 2 if closed_channel is None else closed_channel
     c.bn_dw[BN_SCALE, c.zero_channels] = 0.0
     c.bn_dw[BN_BETA, c.zero_channels] = 0.0
     c.bn_dw[BN_BETA, c.closed_channel] = -50.0
