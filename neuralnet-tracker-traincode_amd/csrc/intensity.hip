@@ -10,7 +10,8 @@
 // prm[B][TTK_INTENSITY_PARAMS]; a disabled operation costs nothing.  The formulas restate kornia's published
 // implementations (kornia.enhance.equalize / posterize / adjust_gamma / adjust_contrast / adjust_brightness,
 // kornia.filters.gaussian_blur2d with border_type="reflect"); kornia itself is not available to this build: PARITY
-// UNPINNED, the checker is oracle/intensity.py.
+// UNPINNED, the checkers are oracle/intensity.py (float32) and the float64 reference of tests/intensity_ref.py, whose
+// equalize is pinned to a literal torch restatement of kornia's _scale_channel (tests/test_intensity_ref.py).
 #include "ttk_common.h"
 
 namespace ttk {
@@ -59,7 +60,8 @@ __global__ void __launch_bounds__(kIntBlock) intensity_augment_k(const float* __
   __syncthreads();
   if (do_eq) {
     // step = (sum of the non-empty bins - the last non-empty bin) // 255;  lut[k] = (cumsum[k-1] + step // 2) // step,
-    // lut[0] = 0, clamped to 0..255; step == 0 leaves the image alone
+    // lut[0] = 0, clamped to 0..255; step == 0 leaves the image alone (kornia returns fl(fl(x * 255) / 255): the same bits
+    // for the loader's u8 / 256 and for k / 255, at most 1 ulp from x for any other float)
     if (tid == 0) {
       int total = 0, last = 0;
       for (int k = 0; k < 256; ++k) {

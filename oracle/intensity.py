@@ -20,7 +20,10 @@ EQUALIZE, POSTERIZE_BITS, GAMMA, CONTRAST, BRIGHTNESS, BLUR, NOISE_STD, NPARAMS 
 
 def equalize(img: np.ndarray) -> np.ndarray:
     """kornia.enhance.equalize -> _scale_channel: 256-bin histogram of im*255 (torch.histc over [0,255]),
-    step = (sum(non-empty bins) - last non-empty bin) // 255, lut = (cumsum + step//2) // step shifted by one bin."""
+    step = (sum(non-empty bins) - last non-empty bin) // 255, lut = (cumsum + step//2) // step shifted by one bin.
+    step == 0 returns the image itself, as the kernel does; kornia returns fl(fl(x * 255) / 255), the same bits on the lattices
+    k/256 and k/255 and at most 1 ulp away for other floats.  tests/test_intensity_ref.py pins the integer path to a literal
+    torch restatement of _scale_channel (torch.histc, cumsum, //, gather on im.long())."""
     im = (img.astype(F32) * F32(255.0)).astype(F32)
     inside = (im >= 0) & (im <= 255)
     bins = np.minimum((im[inside] * F32(256.0 / 255.0)).astype(np.int64), 255)

@@ -49,8 +49,9 @@ def test_kernel_matches_oracle_on_explicit_parameters(H, W):
     L.call("ttk_intensity_augment", p(dx), p(y), p(dp), p(dn), B, H, W, -0.5)
     got = y.cpu().numpy()
     err = np.abs(got - ref)
-    # tolerance 2e-6 (fp32 pow / blur summation order).  Posterize after gamma/equalize quantises: a 1-ulp difference of
-    # pow can move a pixel across a level - those few pixels are allowed a whole level.
+    # tolerance 2e-6 (fp32 pow / blur summation order) with a trim of 1e-4 of the pixels.  The trim hides what a few pixels do (four
+    # wrong corners per blurred image pass it) and no quantising step follows pow in this chain: the criterion without excluded
+    # pixels is tests/test_intensity_rows_gpu.py; this test stays as the check against the oracle at the training batch's shape.
     bad = err > 2e-6
     assert bad.mean() < 1e-4, f"{bad.sum()} of {bad.size} pixels differ (max {err.max():.3e})"
     for n in range(8):
