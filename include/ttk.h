@@ -9,6 +9,11 @@
  * these symbols with ctypes; INTEGRATION.md shows the binding a maintainer of the reference would
  * add.
  *
+ * The shipped host READS THIS FILE (trackertraincode/_hip.py: parse_header) and derives its argument types and integer constants
+ * from the text, so keep the declarations in their current style: one prototype per `;`, no parentheses inside a parameter list
+ * (callbacks through a typedef), by-value parameters of type int, int64_t, float, double, size_t or unsigned, constants as
+ * `#define TTK_X <integer>` or enumerators with integer values.  The reader refuses what it cannot read; it skips nothing.
+ *
  * Conventions
  *  - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller (PyTorch's
  *    caching allocator in the shipped host code).  The library never allocates, frees or

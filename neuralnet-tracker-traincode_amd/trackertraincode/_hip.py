@@ -1,5 +1,7 @@
 """ctypes binding of libttk_hip.so (C-ABI: include/ttk.h).
 
+The header is the one definition of the ABI: the prototypes bound here and the integer constants (TTK) are read from it, not restated.
+
 There is NO fallback: if the shared object is missing or a symbol is absent, importing the kernels
 raises; an entry point that returns non-zero raises RuntimeError(ttk_last_error_string()).
 """
@@ -9,140 +11,90 @@ import functools
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint, c_void_p
+from typing import NamedTuple
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TTK_LIB") or os.path.join(os.path.dirname(_HERE), "libttk_hip.so")  # TTK_LIB: A/B builds
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "ttk.h")
 
 _P, _I, _L, _F, _D = c_void_p, c_int, c_int64, c_float, c_double
 
-# name -> argument types (the trailing stream pointer is added automatically)
-_SIGNATURES = {
-    "ttk_bn_fwd_finalize": [_P, _P, _I, _I, _L, _P, _P, _P, _P, _P, _F, _F, _P],
-    "ttk_bn_bwd_frozen": [_P, _I],
-    "ttk_bn_frozen_bound": [_P, _P, _I, _I, _L, _P],
-    "ttk_bn_eval_prepare": [_P, _P, _P, _P, _F, _I, _P],
-    "ttk_bn_bwd_finalize": [_P, _I, _I, _L, _P, _P, _P, _P, _I],
-    "ttk_stem_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "ttk_stem_bwd_weight": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I],
-    "ttk_dwconv3x3_fwd": [_P] * 8 + [_I] * 6,
-    "ttk_dwconv3x3_bwd_data": [_P] * 12 + [_I, _P] + [_I] * 6,
-    "ttk_dwconv3x3_fwd_rawskip": [_P] * 9 + [_I] * 5,
-    "ttk_dwconv3x3_bwd_data_rawskip": [_P] * 12 + [_I, _P] + [_I] * 5,
-    "ttk_pwconv1x1_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _I],
-    "ttk_pwconv1x1_bwd_data": [_P] * 8 + [_L, _I, _I, _P, _I],
-    "ttk_pwconv1x1_bwd_weight": [_P] * 7 + [_L, _I, _I, _I],
-    "ttk_pwconv_prepare_weights": [_I, _P, _P, _P, _P],
-    "ttk_pwconv1x1_bwd_fused": [_P] * 11 + [_L, _I, _I],
-    "ttk_transpose": [_P, _P, _I, _I],
-    "ttk_avgpool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I],
-    "ttk_avgpool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "ttk_avgpool_fwd_rawskip": [_P, _P, _P, _P, _P, _I, _I, _I],
-    "ttk_avgpool_bwd_rawskip": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "ttk_bn_act": [_P, _P, _P, _P, _L, _I],
-    "ttk_stem7_fwd": [_P, _P, _P, _P, _P, _I, _I, _I],
-    "ttk_stem7_bwd_weight": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "ttk_maxpool3x3s2_fwd": [_P, _P, _P, _P, _I, _I, _I, _I],
-    "ttk_maxpool3x3s2_bwd": [_P] * 7 + [_I] * 4,
-    "ttk_bn_add_act": [_P, _P, _P, _P, _P, _P, _I, _L, _I],
-    "ttk_residual_bwd": [_P] * 10 + [_L, _I],
-    "ttk_bn_bwd_apply": [_P, _P, _P, _P, _L, _I],
-    "ttk_conv_weight_repack": [_P, _P, _P, _I, _I, _I, _I],
-    "ttk_conv_prepare_weights": [_I, _P, _P, _P, _P, _P, _P],
-    "ttk_conv_fwd": [_P, _P, _P, _P, _P, _P] + [_I] * 9,
-    "ttk_conv_bwd_data": [_P] * 8 + [_I] * 9,
-    "ttk_conv_bwd_weight": [_P] * 7 + [_I] * 9,
-    "ttk_heads_fwd": [_P] * 8 + [_I] * 7 + [_P] * 9,
-    "ttk_heads_bwd": [_P] * 8 + [_I] * 7 + [_P] * 15,
-    "ttk_diag_scale_fwd": [_P, _P, _I],
-    "ttk_diag_scale_bwd": [_P, _P, _P, _I],
-    "ttk_loss_rot_fwd": [_P, _P, _I, _P],
-    "ttk_loss_rot_bwd": [_P, _P, _P, _I, _P],
-    "ttk_loss_rot6d_fwd": [_P, _P, _I, _P],
-    "ttk_loss_rot6d_bwd": [_P, _P, _I, _P],
-    "ttk_loss_ortho6d_fwd": [_P, _I, _P],
-    "ttk_loss_ortho6d_bwd": [_P, _P, _I, _P],
-    "ttk_mat_to_quat_fwd": [_P, _I, _P],
-    "ttk_mat_to_quat_bwd": [_P, _P, _I, _P],
-    "ttk_loss_quatreg_fwd": [_P, _I, _P],
-    "ttk_loss_quatreg_bwd": [_P, _P, _I, _P],
-    "ttk_loss_mse_rows_fwd": [_P, _P, _I, _I, _P],
-    "ttk_loss_mse_rows_bwd": [_P, _P, _P, _I, _I, _P],
-    "ttk_loss_mse_cols_fwd": [_P, _P, _I, _I, _I, _I, _P],
-    "ttk_loss_mse_cols_bwd": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "ttk_multi_copy": [_I, _P, _P, _P],
-    "ttk_weighted_sum_fwd": [_I, _P, _P, _P, _P, _F, _P],
-    "ttk_weighted_sum_bwd": [_I, _P, _P, _P, _P, _F, _P],
-    "ttk_loss_points_fwd": [_P, _P, _I, _I, _F, _F, _P],
-    "ttk_loss_points_bwd": [_P, _P, _P, _I, _I, _F, _F, _P],
-    "ttk_loss_nllrot_fwd": [_P, _P, _P, _I, _P],
-    "ttk_loss_nllrot_bwd": [_P, _P, _P, _P, _I, _P, _P],
-    "ttk_loss_nllcoord_fwd": [_P, _P, _P, _I, _P],
-    "ttk_loss_nllcoord_bwd": [_P, _P, _P, _P, _I, _P, _P],
-    "ttk_loss_normal_fwd": [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P],
-    "ttk_loss_normal_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P],
-    "ttk_loss_laplace_fwd": [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P],
-    "ttk_loss_laplace_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P],
-    "ttk_loss_elem_fwd": [_P, _P, _P, _I, _I, _I, _F, _P],
-    "ttk_loss_elem_bwd": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
-    "ttk_loss_rot_geodesic_fwd": [_P, _P, _I, _P],
-    "ttk_loss_rot_geodesic_bwd": [_P, _P, _P, _I, _P],
-    "ttk_loss_gmm_fwd": [_P, _P, _P, _P, _I, _D, _I, _P, _P],
-    "ttk_loss_gmm_bwd": [_P, _P, _P, _P, _I, _D, _P, _I, _P],
-    "ttk_loss_batch": [_I, _P],
-    "ttk_loss_batch_rows": [_I, _P, _P, _P],
-    "ttk_row_weights": [_P, _P, _P, _I, _I, _P],
-    "ttk_blur3x3_fwd": [_P, _P, _I, _I, _I, _I, _I],
-    "ttk_blur3x3_bwd": [_P, _P, _P, _I, _I, _I, _I, _I],
-    "ttk_view_roi": [_P, _P, _P, _F, _I, _P],
-    "ttk_roi_transform": [_P, _P, _I, _I, _P],
-    "ttk_affine_warp": [_P, _I, _I, _I, _I, _P, _P, _I, _F, _F],
-    "ttk_area_crop": [_P, _I, _I, _I, _I, _P, _P, _I, _F, _F],
-    "ttk_affine_labels": [_P, _I, _I, _P, _P, _P, _P, _P],
-    "ttk_affine_labels2d": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "ttk_ensemble_reduce": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
-    "ttk_track_crop": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P],
-    "ttk_track_update": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "ttk_facefit_objective": [_P] * 8 + [_I, _I, _I, _P, _P],
-    "ttk_facefit": [_P] * 8 + [_I, _I, _I, _D, _I, _D, _P, _P, _P, _P, _P],
-    "ttk_intensity_augment": [_P, _P, _P, _P, _I, _I, _I, _F],
-    "ttk_clip_adam": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P],
-    "ttk_clip_adam_guarded": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P],
-    "ttk_stream_probe": [_P, _P, _P, _L, _I, _I, _I, _I, _L, _I, _I, _I],
-    # bf16-compute path (csrc/bc_*.hip)
-    "ttk_bc_prepare_weights": [_I, _P, _P, _P, _P],
-    "ttk_bc_pw_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I],
-    "ttk_bc_pw_bwd_data": [_P] * 8 + [_L, _I, _I],
-    "ttk_bc_pw_bwd_weight": [_P] * 7 + [_L, _I, _I],
-    "ttk_bc_pw_bwd_fused": [_P] * 10 + [_L, _I, _I],
-    "ttk_bc_dw_fwd": [_P] * 8 + [_I] * 5,
-    "ttk_bc_avgpool_fwd": [_P, _P, _P, _P, _I, _I, _I],
-    "ttk_bc_avgpool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "ttk_bc_dw_bwd_data": [_P] * 12 + [_I, _P] + [_I] * 5,
-    "ttk_bc_bn_bwd_finalize_fold": [_P, _I, _I, _L, _P, _P, _P, _P, _I, _P, _I, _L, _P, _I],
-    # any-channel-count family (csrc/anyc_*.hip): width-scaled MobileNet backbones
-    "ttk_anyc_stem_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "ttk_anyc_stem_bwd_weight": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I],
-    "ttk_anyc_dw_fwd": [_P] * 8 + [_I] * 5,
-    "ttk_anyc_dw_bwd_data": [_P] * 12 + [_I, _P] + [_I] * 5,
-    "ttk_anyc_pw_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I],
-    "ttk_anyc_pw_bwd_data": [_P] * 8 + [_L, _I, _I],
-    "ttk_anyc_pw_bwd_weight": [_P] * 6 + [_I, _P, _L, _I, _I],
-    "ttk_anyc_avgpool_fwd": [_P, _P, _P, _P, _I, _I, _I],
-    "ttk_anyc_avgpool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "ttk_anyc_bn_act": [_P, _P, _P, _P, _L, _I],
-}
-
-ABI_VERSION = 38
-
-ADAM_HEALTH_SKIPPED, ADAM_HEALTH_CONSECUTIVE, ADAM_HEALTH_CULPRIT, ADAM_HEALTH_WORDS = 0, 1, 2, 4  # TTK_ADAM_HEALTH_*
+# by-value C types of the header; anything with a `*` binds as c_void_p (a `const char*` return as c_char_p)
+_CTYPES = {"int": _I, "int64_t": _L, "float": _F, "double": _D, "size_t": c_size_t, "unsigned": c_uint, "ttk_stream_t": _P,
+           "ttk_mobilenet_ready_fn": _P}
+_C_TYPE_WORDS = set(_CTYPES) | {"void", "char", "short", "long", "signed"}
 
 
-MOBILENET_MAX_BLOCKS, MOBILENET_MAX_BUFFERS = 16, 96  # TTK_MOBILENET_MAX_BLOCKS, TTK_MOBILENET_MAX_BUFFERS
-MOBILENET_MODES = {"train": 0, "frozen": 1, "eval": 2}   # TTK_MOBILENET_TRAIN / _FROZEN / _EVAL
-MOBILENET_PRECISIONS = {"fp32": 0, "bf16-compute": 1}    # TTK_MOBILENET_FP32 / _BF16_COMPUTE
+class Prototype(NamedTuple):
+    restype: type
+    argtypes: list   # every parameter, the stream included
+    stream: bool     # the last parameter is a ttk_stream_t: an entry point that launches (call())
+
+
+def _ctype(decl: str, fn: str, ret: bool = False):
+    """One parameter (`const float* const* w`, `int64_t M`, `float`) or return declaration -> its ctypes class."""
+    if "*" in decl:
+        return c_char_p if ret and re.sub(r"\s|\bconst\b", "", decl) == "char*" else _P
+    words = [w for w in decl.split() if w != "const"]
+    if len(words) > 1 and words[-1] not in _C_TYPE_WORDS:
+        words.pop()  # the parameter's name
+    if " ".join(words) not in _CTYPES:
+        raise RuntimeError(f"{fn}: the binding has no ctypes type for `{decl.strip()}` (_hip._CTYPES)")
+    return _CTYPES[" ".join(words)]
+
+
+def parse_header(text: str) -> tuple[dict[str, Prototype], dict[str, int]]:
+    """The C ABI as include/ttk.h declares it -> (prototypes by name, integer constants by name without the TTK_ prefix: every
+    `#define TTK_X <integer>` and every enumerator).  Relies on the header's style: one prototype per `;`, no parentheses inside a
+    parameter list.  A declaration it cannot read raises and names the function; it never skips one."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2], 0) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+TTK_(\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", text, re.M)}
+    for body in re.findall(r"\benum\s*\w*\s*\{([^}]*)\}", text):
+        value = 0
+        for item in filter(None, map(str.strip, body.split(","))):
+            name, _, explicit = map(str.strip, item.partition("="))
+            value = int(explicit, 0) if explicit else value
+            consts[name.removeprefix("TTK_")] = value
+            value += 1
+    protos = {}
+    for stmt in re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M).split(";"):
+        named = re.search(r"\b(ttk_\w+)\s*\(", stmt)
+        if named is None or stmt.split()[0] == "typedef":
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(ttk_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if m is None:
+            raise RuntimeError(f"{named[1]}: the binding cannot read this declaration (one prototype per `;`, no nested parentheses)")
+        params = [] if m[3].strip() in ("", "void") else m[3].split(",")
+        protos[m[2]] = Prototype(_ctype(m[1], m[2], ret=True), [_ctype(p, m[2]) for p in params],
+                                 bool(params) and params[-1].split()[0] == "ttk_stream_t")
+    return protos, consts
+
+
+def read_header(path: str):
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the ctypes binding is derived from the C header of libttk_hip.so (include/ttk.h of the source "
+                           "tree). There is no second definition of the ABI to fall back to.")
+    with open(path) as f:
+        return parse_header(f.read())
+
+
+# Read once, when this module is imported: the constants size the ctypes structures below.  (TTK_LIB builds are bound by the tree's header
+# too; the ABI-version check refuses a library of another version.)
+_PROTOTYPES, TTK = read_header(HEADER_PATH)
+
+# name -> argument types of the launching entry points, without the trailing stream (call() appends it)
+_SIGNATURES = {name: p.argtypes[:-1] for name, p in _PROTOTYPES.items() if p.stream}
+
+ABI_VERSION = TTK["ABI_VERSION"]
+ADAM_HEALTH_SKIPPED, ADAM_HEALTH_CONSECUTIVE, ADAM_HEALTH_CULPRIT, ADAM_HEALTH_WORDS = (
+    TTK["ADAM_HEALTH_" + n] for n in ("SKIPPED", "CONSECUTIVE", "CULPRIT", "WORDS"))
+MOBILENET_MAX_BLOCKS, MOBILENET_MAX_BUFFERS = TTK["MOBILENET_MAX_BLOCKS"], TTK["MOBILENET_MAX_BUFFERS"]
+MOBILENET_MODES = {n: TTK["MOBILENET_" + n.upper()] for n in ("train", "frozen", "eval")}
+MOBILENET_PRECISIONS = {"fp32": TTK["MOBILENET_FP32"], "bf16-compute": TTK["MOBILENET_BF16_COMPUTE"]}
 
 
 class MobileNetPlan(ctypes.Structure):
@@ -166,19 +118,31 @@ class LossOp(ctypes.Structure):
     _fields_ = [("kind", c_int), ("items", c_int), ("p", c_void_p * 6), ("i", c_int * 4), ("f", c_float * 2), ("d", c_double)]
 
 
-LOSS_BATCH_MAX = 32
-# entry point -> (TTK_OP_* kind, threads the op needs as a function of its argument tuple); the arguments are packed into
-# p[] / i[] / f[] / d in signature order
+LOSS_BATCH_MAX = TTK["LOSS_BATCH_MAX"]
+# entry point ttk_loss_<name> -> (kind TTK_OP_<NAME>, threads the op needs as a function of its argument tuple); the arguments are
+# packed into p[] / i[] / f[] / d in signature order
 _n = lambda k: (lambda a: a[k])
-LOSS_BATCH_OPS = {
-    "ttk_loss_rot_fwd": (0, _n(2)), "ttk_loss_rot_bwd": (1, _n(3)), "ttk_loss_rot6d_fwd": (2, _n(2)), "ttk_loss_rot6d_bwd": (3, _n(2)),
-    "ttk_loss_ortho6d_fwd": (4, _n(1)), "ttk_loss_ortho6d_bwd": (5, _n(2)), "ttk_loss_quatreg_fwd": (6, _n(1)), "ttk_loss_quatreg_bwd": (7, _n(2)),
-    "ttk_loss_mse_rows_fwd": (8, lambda a: a[2] * 64), "ttk_loss_mse_rows_bwd": (9, lambda a: a[3] * a[4]),
-    "ttk_loss_mse_cols_fwd": (10, lambda a: a[2] * 64), "ttk_loss_mse_cols_bwd": (11, lambda a: a[3] * a[4]),
-    "ttk_loss_points_fwd": (12, lambda a: a[2] * 64), "ttk_loss_points_bwd": (13, lambda a: a[3] * 204),
-    "ttk_loss_nllrot_fwd": (14, _n(3)), "ttk_loss_nllrot_bwd": (15, _n(4)), "ttk_loss_nllcoord_fwd": (16, _n(3)), "ttk_loss_nllcoord_bwd": (17, _n(4)),
-    "ttk_loss_normal_fwd": (18, lambda a: a[3] * 64), "ttk_loss_normal_bwd": (19, lambda a: a[4] * (204 if a[6] else a[5])),
-    "ttk_loss_gmm_fwd": (20, lambda a: a[6] * 64), "ttk_loss_gmm_bwd": (21, lambda a: a[7] * 50),
+LOSS_BATCH_OPS = {"ttk_loss_" + name: (TTK["OP_" + name.upper()], items) for name, items in {
+    "rot_fwd": _n(2), "rot_bwd": _n(3), "rot6d_fwd": _n(2), "rot6d_bwd": _n(2),
+    "ortho6d_fwd": _n(1), "ortho6d_bwd": _n(2), "quatreg_fwd": _n(1), "quatreg_bwd": _n(2),
+    "mse_rows_fwd": lambda a: a[2] * 64, "mse_rows_bwd": lambda a: a[3] * a[4],
+    "mse_cols_fwd": lambda a: a[2] * 64, "mse_cols_bwd": lambda a: a[3] * a[4],
+    "points_fwd": lambda a: a[2] * 64, "points_bwd": lambda a: a[3] * 204,
+    "nllrot_fwd": _n(3), "nllrot_bwd": _n(4), "nllcoord_fwd": _n(3), "nllcoord_bwd": _n(4),
+    "normal_fwd": lambda a: a[3] * 64, "normal_bwd": lambda a: a[4] * (204 if a[6] else a[5]),
+    "gmm_fwd": lambda a: a[6] * 64, "gmm_bwd": lambda a: a[7] * 50,
+}.items()}
+
+# The one hand-written part of the binding: pointer parameters of the ttk_mobilenet_* family that bind TYPED (callers pass a MobileNetPlan,
+# int arrays, a callback) instead of as c_void_p.  function -> {parameter index: type}; everything else of these functions is the header's.
+_PLAN_P, _INT_P = ctypes.POINTER(MobileNetPlan), ctypes.POINTER(c_int)
+_TYPED_POINTERS = {
+    "ttk_mobilenet_plan_init": {0: _PLAN_P, 6: _INT_P, 7: _INT_P, 8: _INT_P, 9: _INT_P},
+    "ttk_mobilenet_forward_workspace_bytes": {0: _PLAN_P},
+    "ttk_mobilenet_backward_workspace_bytes": {0: _PLAN_P},
+    "ttk_mobilenet_describe": {0: _PLAN_P, 2: c_char_p, 4: ctypes.POINTER(c_size_t)},
+    "ttk_mobilenet_forward": {0: _PLAN_P},
+    "ttk_mobilenet_backward": {0: _PLAN_P, 12: MOBILENET_READY_FN},
 }
 
 
@@ -191,63 +155,26 @@ class _Library:
                 "neuralnet-tracker-traincode_amd/csrc`). There is no CPU/PyTorch fallback for the training path."
             )
         self.cdll = ctypes.CDLL(LIB_PATH)
-        self.cdll.ttk_last_error_string.restype = c_char_p
-        self.cdll.ttk_abi_version.restype = c_int
-        self.cdll.ttk_clear_error.restype = c_int
-        self._clear = self.cdll.ttk_clear_error
         v = self.cdll.ttk_abi_version()
         if v != ABI_VERSION:
             raise RuntimeError(f"libttk_hip.so ABI version {v}, host expects {ABI_VERSION}: rebuild")
-        for name in ("ttk_partial_rows_elementwise", "ttk_partial_rows_gemm"):
-            fn = getattr(self.cdll, name)
-            fn.argtypes, fn.restype = [c_int64], c_int
-        self.cdll.ttk_partial_rows_pwconv.argtypes, self.cdll.ttk_partial_rows_pwconv.restype = [c_int64, c_int, c_int, c_int], c_int
-        self.cdll.ttk_pwconv_tile_rows.argtypes, self.cdll.ttk_pwconv_tile_rows.restype = [c_int64, c_int, c_int, c_int], c_int
-        self.cdll.ttk_heads_num_rows.argtypes, self.cdll.ttk_heads_num_rows.restype = [c_int, c_int, c_int], c_int
-        self.cdll.ttk_pwconv_prepared_bytes.argtypes, self.cdll.ttk_pwconv_prepared_bytes.restype = [c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_partial_rows_dwconv.argtypes, self.cdll.ttk_partial_rows_dwconv.restype = [c_int] * 6, c_int
-        self.cdll.ttk_pwconv_wgrad_partial_bytes.argtypes, self.cdll.ttk_pwconv_wgrad_partial_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_pwconv_wgrad_scratch_bytes.argtypes, self.cdll.ttk_pwconv_wgrad_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_conv_wgrad_partial_bytes.argtypes, self.cdll.ttk_conv_wgrad_partial_bytes.restype = [c_int] * 9, ctypes.c_size_t
-        self.cdll.ttk_pwconv1x1_bwd_fused_rows.argtypes, self.cdll.ttk_pwconv1x1_bwd_fused_rows.restype = [c_int64, c_int, c_int], c_int
-        self.cdll.ttk_pwconv1x1_bwd_fused_partial_bytes.argtypes, self.cdll.ttk_pwconv1x1_bwd_fused_partial_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_stem7_wgrad_partial_bytes.argtypes, self.cdll.ttk_stem7_wgrad_partial_bytes.restype = [c_int] * 3, ctypes.c_size_t
-        self.cdll.ttk_stem_wgrad_partial_bytes.argtypes, self.cdll.ttk_stem_wgrad_partial_bytes.restype = [], ctypes.c_size_t
-        self.cdll.ttk_bc_prepared_bytes.argtypes, self.cdll.ttk_bc_prepared_bytes.restype = [c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_bc_partial_rows_pw.argtypes, self.cdll.ttk_bc_partial_rows_pw.restype = [c_int64, c_int, c_int], c_int
-        self.cdll.ttk_bc_partial_rows_dw.argtypes, self.cdll.ttk_bc_partial_rows_dw.restype = [c_int] * 6, c_int
-        self.cdll.ttk_bc_partial_rows_pool.argtypes, self.cdll.ttk_bc_partial_rows_pool.restype = [c_int] * 3, c_int
-        self.cdll.ttk_bc_pw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_bc_pw_wgrad_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_bc_pw_bwd_fused_rows.argtypes, self.cdll.ttk_bc_pw_bwd_fused_rows.restype = [c_int64, c_int, c_int], c_int
-        self.cdll.ttk_bc_pw_wgrad_slices.argtypes, self.cdll.ttk_bc_pw_wgrad_slices.restype = [c_int64, c_int, c_int], c_int
-        self.cdll.ttk_bc_pw_bwd_fused_scratch_bytes.argtypes, self.cdll.ttk_bc_pw_bwd_fused_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
-        self.cdll.ttk_anyc_partial_rows.argtypes, self.cdll.ttk_anyc_partial_rows.restype = [c_int64], c_int
-        self.cdll.ttk_anyc_stem_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_stem_wgrad_scratch_bytes.restype = [c_int] * 4, ctypes.c_size_t
-        self.cdll.ttk_anyc_dw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_dw_wgrad_scratch_bytes.restype = [c_int] * 4, ctypes.c_size_t
-        self.cdll.ttk_anyc_pw_wgrad_scratch_bytes.argtypes, self.cdll.ttk_anyc_pw_wgrad_scratch_bytes.restype = [c_int64, c_int, c_int], ctypes.c_size_t
-        PP = ctypes.POINTER(MobileNetPlan)
-        self.cdll.ttk_mobilenet_plan_init.argtypes = [PP] + [c_int] * 5 + [ctypes.POINTER(c_int)] * 4 + [c_int] * 3
-        self.cdll.ttk_mobilenet_plan_init.restype = c_int
-        for name in ("ttk_mobilenet_forward_workspace_bytes", "ttk_mobilenet_backward_workspace_bytes"):
-            getattr(self.cdll, name).argtypes, getattr(self.cdll, name).restype = [PP], ctypes.c_size_t
-        self.cdll.ttk_mobilenet_describe.argtypes = [PP, c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-        self.cdll.ttk_mobilenet_describe.restype = c_int
-        self.cdll.ttk_mobilenet_plan_bytes.argtypes, self.cdll.ttk_mobilenet_plan_bytes.restype = [], ctypes.c_size_t
+        self._fns = {}  # what call() launches: the entry points that end in a stream
+        self._stale_reported = False
+        for name, typed in _TYPED_POINTERS.items():
+            declared = _PROTOTYPES[name].argtypes if name in _PROTOTYPES else []
+            if any(i >= len(declared) or declared[i] is not _P for i in typed):
+                raise RuntimeError(f"_hip._TYPED_POINTERS[{name!r}] types a parameter that include/ttk.h does not declare as a pointer")
+        for name, proto in _PROTOTYPES.items():
+            fn = getattr(self.cdll, name)  # AttributeError if the symbol is missing: loud by design
+            typed = _TYPED_POINTERS.get(name, {})
+            fn.argtypes = [typed.get(i, ty) for i, ty in enumerate(proto.argtypes)]
+            fn.restype = proto.restype
+            if proto.stream:
+                self._fns[name] = fn
+        self._clear = self.cdll.ttk_clear_error
         if self.cdll.ttk_mobilenet_plan_bytes() != ctypes.sizeof(MobileNetPlan):
             raise RuntimeError(f"ttk_mobilenet_plan is {self.cdll.ttk_mobilenet_plan_bytes()} bytes in libttk_hip.so, {ctypes.sizeof(MobileNetPlan)} in "
                                "_hip.MobileNetPlan: the two definitions differ")
-        self.cdll.ttk_mobilenet_forward.argtypes = [PP, _P, _P, _I, _P, _I, _P, _F, _F, _P, ctypes.c_size_t, _P, _P]
-        self.cdll.ttk_mobilenet_forward.restype = c_int
-        self.cdll.ttk_mobilenet_backward.argtypes = [PP, _P, _P, _P, _I, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, ctypes.c_size_t,
-                                                     MOBILENET_READY_FN, _P, _P]
-        self.cdll.ttk_mobilenet_backward.restype = c_int
-        self._fns = {}
-        self._stale_reported = False
-        for name, sig in _SIGNATURES.items():
-            fn = getattr(self.cdll, name)  # AttributeError if the symbol is missing: loud by design
-            fn.argtypes = list(sig) + [c_void_p]
-            fn.restype = c_int
-            self._fns[name] = fn
 
     def clear_stale_error(self, where: str = "") -> int:
         """Drops (and reports once) a HIP error that an EARLIER, unrelated call of the process left pending - entry points report launch
@@ -551,11 +478,4 @@ def from_blocks64(t: torch.Tensor) -> torch.Tensor:
 
 
 def exported_symbols() -> list[str]:
-    return ["ttk_abi_version", "ttk_last_error_string", "ttk_clear_error", "ttk_partial_rows_elementwise",
-            "ttk_partial_rows_gemm", "ttk_partial_rows_pwconv", "ttk_pwconv_tile_rows", "ttk_partial_rows_dwconv", "ttk_heads_num_rows", "ttk_pwconv_prepared_bytes",
-            "ttk_pwconv_wgrad_partial_bytes", "ttk_pwconv_wgrad_scratch_bytes", "ttk_stem_wgrad_partial_bytes", "ttk_conv_wgrad_partial_bytes", "ttk_stem7_wgrad_partial_bytes",
-            "ttk_pwconv1x1_bwd_fused_rows", "ttk_pwconv1x1_bwd_fused_partial_bytes", "ttk_bc_prepared_bytes", "ttk_bc_partial_rows_pw",
-            "ttk_bc_partial_rows_dw", "ttk_bc_partial_rows_pool", "ttk_bc_pw_wgrad_scratch_bytes", "ttk_bc_pw_bwd_fused_rows",
-            "ttk_bc_pw_bwd_fused_scratch_bytes", "ttk_bc_pw_wgrad_slices", "ttk_anyc_partial_rows", "ttk_anyc_stem_wgrad_scratch_bytes",
-            "ttk_anyc_dw_wgrad_scratch_bytes", "ttk_anyc_pw_wgrad_scratch_bytes", "ttk_mobilenet_plan_init", "ttk_mobilenet_plan_bytes", "ttk_mobilenet_forward_workspace_bytes",
-            "ttk_mobilenet_backward_workspace_bytes", "ttk_mobilenet_forward", "ttk_mobilenet_backward", "ttk_mobilenet_describe"] + list(_SIGNATURES)
+    return list(_PROTOTYPES)

@@ -18,7 +18,7 @@ import torch
 
 from .. import _hip
 
-_BF = 3          # TTK_STORE_ACT_BF16 | TTK_STORE_GRAD_BF16 (stem: C = 32, the same bytes in either block size)
+_BF = _hip.TTK["STORE_ACT_BF16"] | _hip.TTK["STORE_GRAD_BF16"]  # (stem: C = 32, the same bytes in either block size)
 _DT = torch.bfloat16
 
 

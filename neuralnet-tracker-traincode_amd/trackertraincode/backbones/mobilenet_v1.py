@@ -187,7 +187,7 @@ def _check_native_product():
                              f'value is {value!r}; use sequence "python" for this experiment')
 
 
-_BN_ROWS = 8  # TTK_BN_ROWS: scale, beta, mean, rstd, ga, gb, gmean, (pad) - see include/ttk.h
+_BN_ROWS = _hip.TTK["BN_ROWS"]  # scale, beta, mean, rstd, ga, gb, gmean, aux - see include/ttk.h
 
 
 class _BnArena:
@@ -245,7 +245,7 @@ class _Ctx:
     __slots__ = ("x", "stages", "a_in", "part", "dims", "pool_skip", "wparams", "HW", "B", "prep", "bf16_compute", "frozen", "blur", "blocks")
 
 
-_FP32_STORAGE = 0  # the trailing TTK_STORE_* argument of the fp32 entry points: fp32 tensors (the bf16 storage variants under these kernels are retired)
+_FP32_STORAGE = 0  # the trailing TTK_STORE_* argument of the fp32 entry points with NO bit set (the header names the bits, not their absence): fp32 tensors
 
 
 def _check_forward_inputs(x, params, buffers, blur, nblocks):
@@ -286,8 +286,8 @@ def _identity_bn(C, device):
     key = (device.type, device.index, C)
     if key not in _IDENTITY_BN:
         t = torch.zeros((_BN_ROWS, C), dtype=torch.float32, device=device)
-        t[0] = 1.0
-        t[3] = 1.0
+        t[_hip.TTK["BN_SCALE"]] = 1.0
+        t[_hip.TTK["BN_RSTD"]] = 1.0
         _IDENTITY_BN[key] = t
     return _IDENTITY_BN[key].clone()
 

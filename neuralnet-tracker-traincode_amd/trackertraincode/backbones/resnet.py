@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from .. import _hip
 from ..neuralnets.modelcomponents import BlurPool2D
 
-_BN_ROWS = 8
+_BN_ROWS = _hip.TTK["BN_ROWS"]
 _PLAN = [(64, 1), (64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1)]  # (planes, stride) per BasicBlock
 
 

@@ -24,7 +24,7 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/ttk.h but not exported"
     import trackertraincode._hip as H
 
-    assert set(H.exported_symbols()) <= set(declared)
+    assert set(H.exported_symbols()) == set(declared)
     lib.ttk_abi_version.restype = ctypes.c_int
     assert lib.ttk_abi_version() == H.ABI_VERSION
 
