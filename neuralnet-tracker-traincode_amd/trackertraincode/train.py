@@ -816,182 +816,155 @@ class GraphedTrainStep:
         if layout not in ("per_tag", "flat"):
             raise ValueError(f"GraphedTrainStep: layout {layout!r} (per_tag | flat)")
         self.layout = layout
-        self._flat: dict = {}       # flat layout: static [B, ...] buffer per field
-        self._fields: dict = {}     # flat layout: field -> (trailing shape, dtype), every field seen so far
-        self._codes: dict = {}      # flat layout: Tag code -> int32 [B] device tensor filled with it (source of the per-row codes)
-        self._tables = None         # flat layout: FlatLoss
         self.model, self.criterions, self.optimizer = model, criterions, optimizer
         self.graph = None
         self._sig = None
-        self._static: list[Batch] = []
+        self._static: list[Batch] = []  # the graph's static inputs: per-Tag one Batch per sub-batch, flat ONE Batch of [B, ...] buffers
         self._out = None
         self.captures = 0
         self._miss_streak = 0      # consecutive steps whose signature differed from the captured one
         self.eager_only = False    # set once re-capturing is seen to happen step after step
+        # flat layout only; none of it refers to a static input
+        self._tables = None        # FlatLoss
+        self._fields: dict = {}    # field -> (trailing shape, dtype), every field seen so far
+        self._fill: dict = {}      # [B] sources of what no sub-batch carries: Tag code -> int32 vector filled with it, "ones" -> float32 ones
 
+    # ---- what the two layouts differ in: signature, step function, static inputs, which source goes to which of them -----------------------
     def _signature(self, batches, epoch):
-        layout = tuple((str(b.meta.tag), b.meta.batchsize, tuple((k, tuple(v.shape), str(v.dtype)) for k, v in b.items()))
-                       for b in batches)
-        return layout, _criterion_weights(self.criterions, epoch), self.model.training
-
-    def _eager(self, batches, epoch):
-        self.optimizer.zero_grad(set_to_none=True)
-        out = training_step(self.model, batches, epoch, self.criterions)
-        out["loss"].backward()
-        self.optimizer.step()
-        return out
-
-    def _capture(self, batches, epoch):
-        # static inputs: the fields every sub-batch has (image, coord_convention_id, ...) are views of ONE tensor per field, in sub-batch
-        # order, so that training_step's concatenation over the sub-batches is a view (_concat_rows) instead of a copy per step
-        shared = set.intersection(*[set(k for k, v in b.items() if torch.is_tensor(v)) for b in batches]) if len(batches) > 1 else set()
-        joined = {k: torch.concat([b[k] for b in batches], dim=0).split([int(b[k].shape[0]) for b in batches], dim=0) for k in shared
-                  if all(b[k].dim() >= 1 and b[k].shape[1:] == batches[0][k].shape[1:] and b[k].dtype == batches[0][k].dtype for b in batches)}
-        self._static = [Batch(b.meta, ((k, joined[k][i] if k in joined else v.clone()) for k, v in b.items())) for i, b in enumerate(batches)]
-        self.optimizer.sync_hyper_to_device()
-        self.graph = torch.cuda.CUDAGraph()
-        self.optimizer.zero_grad(set_to_none=True)  # gradients are allocated from the graph's pool at fixed addresses
-        with _hip.CAPTURE_LOCK:  # (a loader's prefetch thread must not allocate or copy while the capture is open: _hip.CAPTURE_LOCK)
-            with torch.cuda.graph(self.graph):
-                out = training_step(self.model, self._static, epoch, self.criterions)
-                out["loss"].backward()
-                self.optimizer.step()
-        self._out = out
-        self.captures += 1
-
-    def run(self, batches: List[Batch], epoch: int):
-        """One training step.  Returns {"loss", "mt_losses"}; when replayed these are the graph's static output
-        tensors (overwritten by the next call)."""
-        if self.layout == "flat":
-            return self._run_flat(batches, epoch)
-        if self.eager_only:
-            return self._eager(batches, epoch)
-        sig = self._signature(batches, epoch)
-        if sig != self._sig:
-            # A loader that mixes datasets of several Tags draws the per-Tag sub-batch sizes anew every step (ResidentLoader): the signature
-            # then changes almost every step and each step would run eagerly AND re-capture (synchronise, capture, a new private pool) -
-            # far slower than eager.  Three misses in a row: stay eager for the rest of the run (round-3 advisor finding).
-            self._miss_streak += 1
-            if self._miss_streak >= 3 and self.captures >= 2:
-                import warnings
-                warnings.warn("GraphedTrainStep: the sub-batch layout changed on three consecutive steps (per-Tag batch sizes vary from step to "
-                              "step?) - a captured graph would be re-captured every step; running eagerly from here on", RuntimeWarning, stacklevel=2)
-                self.eager_only, self.graph, self._static, self._out = True, None, [], None
-                return self._eager(batches, epoch)
-            # first step with this layout: run it eagerly (lazy initialisation, table building, stream creation happen
-            # here and the step counts), then capture for the following steps
-            out = self._eager(batches, epoch)
-            # hand back detached copies and drop the eager autograd graph BEFORE capturing: with it still alive,
-            # hipStreamEndCapture / graph instantiation was seen to segfault on ROCm 7.2 (tools/debug/graph_capture4.py)
-            out = {"loss": out["loss"].detach().clone(), "mt_losses": {k: v.detach().clone() for k, v in out["mt_losses"].items()}}
-            torch.cuda.synchronize()
-            self._capture(batches, epoch)
-            self._sig = sig
-            return out
-        # new batches -> the graph's static inputs: all float32 tensors in one launch (ttk_multi_copy), the rest (ids) one by one
-        fsrc, fdst = [], []
-        for dst, src in zip(self._static, batches):
-            for k, v in src.items():
-                d = dst[k]
-                if v is d or (torch.is_tensor(v) and v.data_ptr() == d.data_ptr() and v.numel() == d.numel()):
-                    continue  # the loader already wrote into the static tensor
-                if (torch.is_tensor(v) and v.is_cuda and v.dtype == d.dtype and v.element_size() % 4 == 0 and v.is_contiguous() and d.is_contiguous()
-                        and v.numel() == d.numel() and v.dim() >= 1 and v.data_ptr() % 4 == 0):
-                    # moved as 32-bit words whatever the dtype (int64 ids, float32 labels): one launch for all of them
-                    fsrc.append(v if v.dtype == torch.float32 else v.view(torch.float32))
-                    fdst.append(d if d.dtype == torch.float32 else d.view(torch.float32))
-                else:
-                    d.copy_(v, non_blocking=True)
-        if fdst:
-            _hip.lib().multi_copy(fsrc, fdst)
-        self._miss_streak = 0
-        self.optimizer.before_graph_replay()
-        self.graph.replay()
-        self.optimizer.after_graph_replay()
-        return self._out
-
-    # ---- flat layout ---------------------------------------------------------------------------------------------------------------
-    def _flat_fields(self, batches):
-        """Adds the tensor fields of `batches` to the fields seen so far; ValueError when a field disagrees with what was seen."""
+        if self.layout == "per_tag":
+            layout = tuple((str(b.meta.tag), b.meta.batchsize, tuple((k, tuple(v.shape), str(v.dtype)) for k, v in b.items()))
+                           for b in batches)
+            return layout, _criterion_weights(self.criterions, epoch), self.model.training
+        # flat: (B, the fields seen so far, model.training) - a Tag that brings a field no earlier step had re-captures
+        B = sum(int(b.meta.prefixshape[0]) for b in batches)
+        if self._tables is None:
+            self._tables = FlatLoss(self.criterions, batches[0]["image"].device)
         for b in batches:
             for k, v in b.items():
                 if torch.is_tensor(v) and k != "tag_code":
                     cur = (tuple(v.shape[1:]), v.dtype)
                     if self._fields.setdefault(k, cur) != cur:
                         raise ValueError(f"GraphedTrainStep(flat): field {k!r} is {cur[0]} {cur[1]} in {b}, {self._fields[k][0]} {self._fields[k][1]} before")
+        return B, tuple(self._fields), self.model.training
 
-    def _flat_copy_in(self, batches):
-        """The sub-batches' fields and Tag codes -> rows of the static buffers: every 32-bit-word tensor in one ttk_multi_copy launch."""
-        as_words = lambda t: t if t.dtype == torch.float32 else t.view(torch.float32)
-        fsrc, fdst = [], []
-        off = 0
+    def _make_static(self, batches):
+        if self.layout == "per_tag":
+            # the fields every sub-batch has (image, coord_convention_id, ...) are views of ONE tensor per field, in sub-batch
+            # order, so that training_step's concatenation over the sub-batches is a view (_concat_rows) instead of a copy per step
+            shared = set.intersection(*[set(k for k, v in b.items() if torch.is_tensor(v)) for b in batches]) if len(batches) > 1 else set()
+            joined = {k: torch.concat([b[k] for b in batches], dim=0).split([int(b[k].shape[0]) for b in batches], dim=0) for k in shared
+                      if all(b[k].dim() >= 1 and b[k].shape[1:] == batches[0][k].shape[1:] and b[k].dtype == batches[0][k].dtype for b in batches)}
+            self._static = [Batch(b.meta, ((k, joined[k][i] if k in joined else v.clone()) for k, v in b.items())) for i, b in enumerate(batches)]
+            return
+        # flat: buffers for every field seen so far, filled with this step's batches
+        B = sum(int(b.meta.prefixshape[0]) for b in batches)
+        dev = batches[0]["image"].device
+        flat = {k: torch.zeros((B,) + trail, dtype=dtype, device=dev) for k, (trail, dtype) in self._fields.items() if k != "dataset_weight"}
+        flat["tag_code"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        flat["dataset_weight"] = torch.ones(B, dtype=torch.float32, device=dev)
+        self._fill = {"ones": torch.ones(B, dtype=torch.float32, device=dev)}
+        self._static = [Batch(Metadata(batches[0].meta._imagesize, batchsize=B, tag=None), flat)]
+        self._copy_in(batches)
+
+    def _pairs(self, batches):
+        """(static tensor, source) for every tensor of `batches`; flat: the sub-batches' rows of the buffers, with one Tag code per row and
+        the dataset weights as float32 (1 where a sub-batch has none)."""
+        if self.layout == "per_tag":
+            yield from ((dst[k], v) for dst, src in zip(self._static, batches) for k, v in src.items())
+            return
+        flat, off = self._static[0], 0
         for b in batches:
             n = int(b.meta.prefixshape[0])
             code = _tag_code(b.meta.tag)
-            if code not in self._codes:  # (first sight of a Tag: one allocation and fill, outside any capture)
-                self._codes[code] = torch.full((self._B,), code, dtype=torch.int32, device=self._flat["tag_code"].device)
-            items = [("tag_code", self._codes[code][:n])] + [(k, v) for k, v in b.items() if torch.is_tensor(v) and k != "tag_code"]
+            if code not in self._fill:  # (first sight of a Tag: one allocation and fill, outside any capture)
+                self._fill[code] = torch.full(flat["tag_code"].shape, code, dtype=torch.int32, device=flat["tag_code"].device)
+            items = [("tag_code", self._fill[code][:n])] + [(k, v) for k, v in b.items() if torch.is_tensor(v) and k != "tag_code"]
             if "dataset_weight" not in b:
-                items.append(("dataset_weight", self._ones[:n]))
+                items.append(("dataset_weight", self._fill["ones"][:n]))
             for k, v in items:
-                d = self._flat[k][off:off + n]
-                if v.dtype != d.dtype and k == "dataset_weight":
-                    v = v.to(d.dtype)
-                if v.is_cuda and v.dtype == d.dtype and v.element_size() % 4 == 0 and v.is_contiguous() and v.numel() == d.numel() and v.data_ptr() % 4 == 0:
-                    if v.numel():
-                        fsrc.append(as_words(v.reshape(n, -1)))
-                        fdst.append(as_words(d.reshape(n, -1)))
-                else:
-                    d.copy_(v.reshape(d.shape), non_blocking=True)
+                d = flat[k][off:off + n]
+                yield d, (v.to(d.dtype) if k == "dataset_weight" else v)
             off += n
-        if fdst:
-            _hip.lib().multi_copy(fsrc, fdst)
 
-    def _flat_eager(self, batches, epoch):
-        self.optimizer.zero_grad(set_to_none=True)
-        self._tables.set_epoch(epoch, replaying=self.graph is not None)
-        out = flat_training_step(self.model, flatten_batches(batches), epoch, self.criterions, self._tables)
+    def _step(self, inputs, epoch):
+        """Forward, losses, backward and optimiser step over `inputs`: launched, or recorded while a capture is open."""
+        if self.layout == "per_tag":
+            out = training_step(self.model, inputs, epoch, self.criterions)
+        else:
+            out = flat_training_step(self.model, inputs[0], epoch, self.criterions, self._tables)
         out["loss"].backward()
         self.optimizer.step()
         return out
 
-    def _run_flat(self, batches: List[Batch], epoch: int):
-        B = sum(int(b.meta.prefixshape[0]) for b in batches)
-        dev = batches[0]["image"].device
-        if self._tables is None:
-            self._tables = FlatLoss(self.criterions, dev)
-        known = len(self._fields)
-        self._flat_fields(batches)
-        sig = (B, self.model.training)
-        if sig != self._sig or len(self._fields) != known:
-            # first step with this batch size / a Tag that brings a field no earlier step had: run it eagerly (lazy initialisation, table
-            # building), then capture over static buffers that hold every field seen so far
-            out = self._flat_eager(batches, epoch)
-            out = {"loss": out["loss"].detach().clone(), "mt_losses": {k: v.detach().clone() for k, v in out["mt_losses"].items()},
-                   "mt_rows": {k: v.clone() for k, v in out["mt_rows"].items()}}
+    # ---- the protocol, once for both ------------------------------------------------------------------------------------------------
+    def _eager(self, batches, epoch):
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.layout == "flat":
+            self._tables.set_epoch(epoch, replaying=self.graph is not None)
+            batches = [flatten_batches(batches)]
+        return self._step(batches, epoch)
+
+    def _capture(self, epoch):
+        self.optimizer.sync_hyper_to_device()
+        self.graph = torch.cuda.CUDAGraph()
+        self.optimizer.zero_grad(set_to_none=True)  # gradients are allocated from the graph's pool at fixed addresses
+        with _hip.CAPTURE_LOCK:  # (a loader's prefetch thread must not allocate or copy while the capture is open: _hip.CAPTURE_LOCK)
+            with torch.cuda.graph(self.graph):
+                out = self._step(self._static, epoch)
+        self._out = out
+        self.captures += 1
+
+    def _copy_in(self, batches):
+        """New batches -> the static inputs.  Whatever can travel as 32-bit words does, whatever its dtype (int64 ids, float32 labels),
+        all in ONE ttk_multi_copy launch, which reads pointers and element counts only; the rest falls back to copy_.  A source that
+        already is its static tensor (the loader wrote into it) and empty tensors need nothing."""
+        words = lambda t: t if t.dtype == torch.float32 else t.view(torch.float32)
+        fsrc, fdst = [], []
+        for d, v in self._pairs(batches):
+            if v is d or (v.numel() == d.numel() and (v.numel() == 0 or v.data_ptr() == d.data_ptr())):
+                continue
+            if (v.is_cuda and v.dtype == d.dtype and v.element_size() % 4 == 0 and v.is_contiguous() and d.is_contiguous()
+                    and v.numel() == d.numel() and v.dim() >= 1 and v.data_ptr() % 4 == 0):
+                fsrc.append(words(v))
+                fdst.append(words(d))
+            else:
+                d.copy_(v.reshape(d.shape), non_blocking=True)
+        if fdst:
+            _hip.lib().multi_copy(fsrc, fdst)
+
+    def run(self, batches: List[Batch], epoch: int):
+        """One training step.  Returns {"loss", "mt_losses"} (flat: and "mt_rows"); when replayed these are the graph's static output
+        tensors (overwritten by the next call)."""
+        if self.eager_only:
+            return self._eager(batches, epoch)
+        sig = self._signature(batches, epoch)
+        if sig != self._sig:
+            # Per-Tag: a loader that mixes datasets of several Tags draws the per-Tag sub-batch sizes anew every step (ResidentLoader): the
+            # signature then changes almost every step and each step would run eagerly AND re-capture (synchronise, capture, a new private
+            # pool) - far slower than eager.  Three misses in a row: stay eager for the rest of the run (round-3 advisor finding).
+            self._miss_streak += 1
+            if self.layout == "per_tag" and self._miss_streak >= 3 and self.captures >= 2:
+                import warnings
+                warnings.warn("GraphedTrainStep: the sub-batch layout changed on three consecutive steps (per-Tag batch sizes vary from step to "
+                              "step?) - a captured graph would be re-captured every step; running eagerly from here on", RuntimeWarning, stacklevel=2)
+                self.eager_only, self.graph, self._static, self._out = True, None, [], None
+                return self._eager(batches, epoch)
+            # first step with this signature: run it eagerly (lazy initialisation, table building, stream creation happen
+            # here and the step counts), then capture for the following steps
+            out = self._eager(batches, epoch)
+            # hand back detached copies and drop the eager autograd graph BEFORE capturing: with it still alive,
+            # hipStreamEndCapture / graph instantiation was seen to segfault on ROCm 7.2 (tools/debug/graph_capture4.py)
+            fresh = lambda t: t.detach().clone()
+            out = {k: fresh(v) if torch.is_tensor(v) else {n: fresh(x) for n, x in v.items()} for k, v in out.items()}
             torch.cuda.synchronize()
-            self._B = B
-            self._flat = {k: torch.zeros((B,) + trail, dtype=dtype, device=dev) for k, (trail, dtype) in self._fields.items() if k != "dataset_weight"}
-            self._flat["tag_code"] = torch.zeros(B, dtype=torch.int32, device=dev)
-            self._flat["dataset_weight"] = torch.ones(B, dtype=torch.float32, device=dev)
-            self._ones = torch.ones(B, dtype=torch.float32, device=dev)
-            self._codes = {}
-            self._flat_copy_in(batches)
-            static = Batch(Metadata(batches[0].meta._imagesize, batchsize=B, tag=None), self._flat)
-            self.optimizer.sync_hyper_to_device()
-            self.graph = torch.cuda.CUDAGraph()
-            self.optimizer.zero_grad(set_to_none=True)
-            with _hip.CAPTURE_LOCK:
-                with torch.cuda.graph(self.graph):  # one stream, no forks
-                    captured = flat_training_step(self.model, static, epoch, self.criterions, self._tables)
-                    captured["loss"].backward()
-                    self.optimizer.step()
-            self._out = captured
-            self.captures += 1
+            self._make_static(batches)
+            self._capture(epoch)
             self._sig = sig
             return out
-        self._flat_copy_in(batches)
-        self._tables.set_epoch(epoch, replaying=True)
+        self._copy_in(batches)
+        self._miss_streak = 0
+        if self.layout == "flat":
+            self._tables.set_epoch(epoch, replaying=True)  # (the weight table is device memory the graph reads, like the learning rates)
         self.optimizer.before_graph_replay()
         self.graph.replay()
         self.optimizer.after_graph_replay()
