@@ -944,6 +944,61 @@ int ttk_facefit(const float* x0, const float* target, const float* weight, const
                 float* pts_out, double* f_out, int* status, int* iters, ttk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The face localizer's inference path (csrc/localizer.hip, csrc/localizer_math.h; reference neuralnets/models.py:30-93 LocalizerNet, the
+ * tracker's first network: it finds the face box in the whole frame).  Additive to ABI 38: no existing entry point changes.
+ * Tensors are planar fp32 [B][C][H][W].  x [B][224][288] is the whitened input, out [B][5] = (face logit, x0, y0, x1, y1) with the box in
+ * the input's [-1, 1] coordinates, attention [B][7][9] (nullable) the softmax map the box is the centre of mass +- deviation of.
+ * Parameter block (float32, ttk_localizer_param_floats() values; the HOST folds every eval-mode BatchNorm into its convolution in float64,
+ * w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps), and rounds once), in this order:
+ *   stem            w[8][3][3], b[8]                          conv 3x3 stride 2 pad 1, 1 -> 8, ReLU
+ *   first pair      w[8][3][3], b[8]; w[8][8], b[8]           depthwise 3x3 + ReLU; 1x1 8 -> 8 without activation
+ *   12 blocks       w1[Cmid][Cin], b1[Cmid]; w2[Cmid][k][k], b2[Cmid]; w3[Cout][Cmid], b3[Cout]
+ *                   (Cin, Cout, k, stride, Cmid / Cin) = (8,12,3,2,2) (12,12,3,1,2) (12,20,3,2,4) (20,20,3,1,4) x 2 (20,32,5,2,2)
+ *                   (32,32,5,1,2) (32,32,3,1,2) x 2 (32,56,3,2,2) (56,56,3,1,2) x 2: expansion 1x1 + ReLU, depthwise k x k (stride,
+ *                   pad k / 2) + ReLU, projection 1x1; the block input is added when Cin == Cout and stride == 1
+ *   head            w[2][56], b[2]; half_size; eps            1x1 56 -> 2 with bias; CenterOfMassAndStd's constants (1.5, 1e-4)
+ *   ttk_localizer_forward  one call, 14 launches (ttk_localizer_launches()) on one stream: stem + first pair, one launch per block - the
+ *                     expanded tensor and the depthwise output of a block live in LDS, the workspace (ttk_localizer_workspace_bytes(B))
+ *                     holds only block inputs and outputs - and the head: logit = mean of map 0, attention = softmax over the 63
+ *                     cells of map 1, mean = half_size * sum(attention * position code), deviation = sqrt(sum(attention * (position
+ *                     code - mean)^2) + eps) - the reference's arithmetic, the unscaled code against the scaled mean - box = mean -+
+ *                     deviation.  Plain fp32 FMAs, every output summed by one thread in a fixed order.
+ *   ttk_localizer_block    the block kernel of the forward alone, with run-time sizes: x [B][Cin][H][W] -> y [B][Cout][ceil(H / stride)]
+ *                     [ceil(W / stride)], params = one block's part of the parameter block.  -1 before anything is launched or written
+ *                     for a null pointer, k outside {3, 5}, stride outside {1, 2}, a channel count outside [1, 112], B outside
+ *                     [1, 65535], H or W outside [1, 4096], or a residual with Cin != Cout or stride 2.
+ *   ttk_localizer_input    frame *t_dev (t_dev == NULL: frame 0) of each of the S sequences of frames[S][T][Hs][Ws] (uint8 with
+ *                     src_is_u8, else float32), letterboxed into x [S][224][288]: uniform scale s = min(288 / Ws, 224 / Hs), centred
+ *                     (ox = (288 - Ws s) / 2, oy = (224 - Hs s) / 2).  Every input pixel is the exact area average of the frame over
+ *                     the pixel's pre-image, outside the frame counting as grey level 0, summed in float64 in a fixed order, rounded
+ *                     to float32, times mul plus add (one fma).  lb[S][3] = (s, ox, oy).  *t_dev outside [0, T): nothing is written.
+ *   ttk_track_reacquire    (csrc/track.hip) re-acquisition of lost lanes in closed loop; one workgroup, enqueued after ttk_track_update
+ *                     of a frame, so it reads t = *t_dev - 1.  loc_out [S][5] and lb [S][3]: the localizer on frame t of every
+ *                     sequence.  The localizer's box in frame pixels (this project's convention, the reference has none): input pixels
+ *                     X = (x + 1) 144, Y = (y + 1) 112, frame pixels ((X - ox) / s, (Y - oy) / s).  Row t of hasface[T][S] =
+ *                     1 / (1 + exp(-logit)) and of loc_roi[T][S][4] = that box.  Per lane l with q = lane_seq[l]:
+ *                       lost_run[l] (int32, zeroed by the caller at the start of a track) = lost[t][l] ? lost_run[l] + 1 : 0;
+ *                       candidate = the box of q clamped to the image as ttk_track_update clamps, VALID by that kernel's rule on the
+ *                         candidate (four finite values before the clamp, w > 0, h > 0, max(w, h) lane_factor[l] >= 2; the same device
+ *                         function);
+ *                       if lost_run[l] >= reacquire_after, the candidate is valid and hasface[t][q] > face_threshold (false for a NaN
+ *                         logit): roi_state[l] = candidate, lost_run[l] = 0, reacquired[t][l] (uint8 [T][L]) = 1; else reacquired = 0.
+ *                     t outside [0, T): nothing is written.  -1 for L outside [1, 16], a null pointer, a size or reacquire_after < 1.
+ * None of the calls synchronises, allocates or uses atomics (graph capturable); two runs are bitwise equal.
+ * ------------------------------------------------------------------------------------------- */
+int ttk_localizer_param_floats(void);
+size_t ttk_localizer_workspace_bytes(int B);
+int ttk_localizer_launches(void);
+int ttk_localizer_forward(const float* x, const float* params, void* workspace, int B, float* out, float* attention, ttk_stream_t stream);
+int ttk_localizer_block(const float* x, const float* params, int B, int H, int W, int Cin, int Cmid, int Cout, int k, int stride, int residual,
+                        float* y, ttk_stream_t stream);
+int ttk_localizer_input(const void* frames, int src_is_u8, int S, int T, int Hs, int Ws, const int* t_dev, float mul, float add, float* x,
+                        float* lb, ttk_stream_t stream);
+int ttk_track_reacquire(const float* loc_out, const float* lb, const int* t_dev, int L, int S, int T, int Hs, int Ws, const int* lane_seq,
+                        const float* lane_factor, const unsigned char* lost, int reacquire_after, float face_threshold, float* roi_state,
+                        int* lost_run, unsigned char* reacquired, float* hasface, float* loc_roi, ttk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Streaming probe (measurement infrastructure: bench.py `copy_probe`, tools/stream_sweep.py; no reference counterpart).
  * Streams `nread` (1, 2 or 5) source tensors of `rows` x `row_bytes`, `stream_bytes` apart, in the access shape of the
  * step's HBM-bound kernels - every workgroup reads `seg_bytes`-wide column slices of consecutive rows, 16 bytes per lane,

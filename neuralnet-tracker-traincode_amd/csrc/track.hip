@@ -12,12 +12,16 @@
 //                  labels_under (label_math.h: the function of the label kernel and of the ensemble reduction) into row *t_dev of the
 //                  trajectory buffers, the reference's clamp, the validity rule, and - after a workgroup barrier - *t_dev + 1.
 //                  Every value is computed serially in one lane: no atomics, bitwise repeatable.
+//   track_reacquire : with a face localizer (localizer.hip) in the loop, after the update: counts every lane's run of lost frames and,
+//                  once it reaches reacquire_after, restarts the lane from the localizer's box if that is a valid box with a face
+//                  probability above the threshold; records the localizer's per-sequence outputs of the frame.
 // Compiled without the SLP vectoriser like heads.hip / ensemble.hip (Makefile): per-sample head math of the same kind.
 #include <math.h>
 
 #include "crop_math.h"
 #include "head_math.h"
 #include "label_math.h"
+#include "localizer_math.h"
 #include "ttk_common.h"
 
 namespace ttk {
@@ -85,13 +89,13 @@ __global__ void __launch_bounds__(kWave* kTrackMaxLanes) track_update_k(const fl
   if (lane < 4) {
     // the reference's clamp (:257-259) and the validity rule, evaluated alike by the four lanes that store the box
     const float x0 = s_lab[l][0], y0 = s_lab[l][1], x1 = s_lab[l][2], y1 = s_lab[l][3];
-    const bool finite = isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1);  // before the clamp: fmaxf(0, NaN) is 0
-    const float c0 = fmaxf(0.f, x0), c1 = fmaxf(0.f, y0), c2 = fminf(x1, (float)Ws), c3 = fminf(y1, (float)Hs);
-    const float w = c2 - c0, h = c3 - c1;
+    float c[4];
+    const bool inside = track_candidate(x0, y0, x1, y1, Ws, Hs, lane_factor[l], c);  // localizer_math.h: shared with track_reacquire_k
+    const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
     // (the back-transformed box is the bounding box of four corners, which re-sorts an inverted prediction: its order is tested on the
     // network's own box)
     const bool ordered = roi[4 * l + 2] > roi[4 * l] && roi[4 * l + 3] > roi[4 * l + 1];
-    const bool valid = finite && ordered && w > 0.f && h > 0.f && fmaxf(w, h) * lane_factor[l] >= 2.f;
+    const bool valid = inside && ordered;
     traj_roi_in[row * 4 + lane] = roi_state[4 * l + lane];
     traj_roi[row * 4 + lane] = s_lab[l][lane];
     if (valid) roi_state[4 * l + lane] = pick4f(c0, c1, c2, c3, lane);
@@ -103,6 +107,41 @@ __global__ void __launch_bounds__(kWave* kTrackMaxLanes) track_update_k(const fl
   }
   __syncthreads();
   if (threadIdx.x == 0) *t_dev = t + 1;
+}
+
+// one workgroup; runs after track_update_k of frame t, so it reads t = *t_dev - 1.  Threads l < L handle the lanes, all threads the rows
+// of the per-sequence outputs.  Every value is computed by one thread: no atomics, bitwise repeatable.
+__global__ void __launch_bounds__(kBlock) track_reacquire_k(const float* __restrict__ loc_out, const float* __restrict__ lb,
+                                                             const int* __restrict__ t_dev, int L, int S, int Tn, int Hs, int Ws,
+                                                             const int* __restrict__ lane_seq, const float* __restrict__ lane_factor,
+                                                             const unsigned char* __restrict__ lost, int reacquire_after, float face_threshold,
+                                                             float* __restrict__ roi_state, int* __restrict__ lost_run,
+                                                             unsigned char* __restrict__ reacquired, float* __restrict__ hasface,
+                                                             float* __restrict__ loc_roi) {
+  const int t = *t_dev - 1;
+  if (t < 0 || t >= Tn) return;
+  for (int q = threadIdx.x; q < S; q += kBlock) {
+    float r[4];
+    localizer_box_to_frame(loc_out + 5 * q + 1, lb + 3 * q, r);
+    hasface[(size_t)t * S + q] = face_probability(loc_out[5 * q]);
+    for (int k = 0; k < 4; ++k) loc_roi[((size_t)t * S + q) * 4 + k] = r[k];
+  }
+  const int l = threadIdx.x;
+  if (l >= L) return;
+  const int q = lane_seq[l];
+  const int run = lost[(size_t)t * L + l] ? lost_run[l] + 1 : 0;
+  bool take = false;
+  float c[4];
+  if (q >= 0 && q < S && run >= reacquire_after) {
+    float r[4];
+    localizer_box_to_frame(loc_out + 5 * q + 1, lb + 3 * q, r);
+    const bool valid = track_candidate(r[0], r[1], r[2], r[3], Ws, Hs, lane_factor[l], c);
+    take = valid && face_probability(loc_out[5 * q]) > face_threshold;  // a NaN logit fails the comparison
+  }
+  if (take)
+    for (int k = 0; k < 4; ++k) roi_state[4 * l + k] = c[k];
+  lost_run[l] = take ? 0 : run;
+  reacquired[(size_t)t * L + l] = take ? 1 : 0;
 }
 
 }  // namespace ttk
@@ -139,6 +178,19 @@ int ttk_track_update(const float* roi, const float* coord, const float* pose, co
   hipLaunchKernelGGL(track_update_k, dim3(1), dim3(kWave * L), 0, (hipStream_t)stream, roi, coord, pose, pts, tr, t_dev, L, N, T, Hs, Ws,
                      lane_factor, roi_state, traj_roi_in, traj_roi, traj_coord, traj_pose, traj_pts, lost);
   TTK_LAUNCH_CHECK("track_update");
+}
+
+int ttk_track_reacquire(const float* loc_out, const float* lb, const int* t_dev, int L, int S, int T, int Hs, int Ws, const int* lane_seq,
+                        const float* lane_factor, const unsigned char* lost, int reacquire_after, float face_threshold, float* roi_state,
+                        int* lost_run, unsigned char* reacquired, float* hasface, float* loc_roi, ttk_stream_t stream) {
+  TTK_REQUIRE(L >= 1 && L <= kTrackMaxLanes, "track_reacquire: 1 <= L <= %d lanes, got %d", kTrackMaxLanes, L);
+  TTK_REQUIRE(loc_out && lb && t_dev && lane_seq && lane_factor && lost && roi_state && lost_run && reacquired && hasface && loc_roi,
+              "track_reacquire: a required pointer is null");
+  TTK_REQUIRE(S > 0 && T > 0 && Hs > 0 && Ws > 0 && reacquire_after >= 1, "track_reacquire: bad sizes (S %d, T %d, frames %d x %d, reacquire_after %d)",
+              S, T, Hs, Ws, reacquire_after);
+  hipLaunchKernelGGL(track_reacquire_k, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, loc_out, lb, t_dev, L, S, T, Hs, Ws, lane_seq, lane_factor,
+                     lost, reacquire_after, face_threshold, roi_state, lost_run, reacquired, hasface, loc_roi);
+  TTK_LAUNCH_CHECK("track_reacquire");
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 """Judge a tracker on a video before shipping it (reference: scripts/evaluate_stability.py).
 
     python scripts/evaluate_stability.py MODE DATA CHECKPOINT... [--factors 1.0 1.2] [--blinks a:b,c:d,...] [--output OUT.npz]
-           [--graphed] [--seed N] [--device cuda]
+           [--graphed] [--seed N] [--device cuda] [--localizer CKPT [--reacquire-after K] [--face-threshold P]]
 
 DATA is a pose shard (datasets/shards.decode_pose_shard) whose frames are one video in order; a CHECKPOINT argument may be a glob (the
 reference's `_find_models`): its matches form one group whose runs are averaged.  Modes:
@@ -10,6 +10,10 @@ reference's `_find_models`): its matches form one group whose runs are averaged.
   closed-loop   every checkpoint tracks the video with `eval.ClosedLoopTracker` - each frame cropped around the box predicted on the
                 previous one, all crop factors as lanes of one track, started from the shard's first box, the whole video enqueued before
                 the one synchronisation (reference :248-264, which reads the box back per frame).  Prints the lost frames per lane.
+                With --localizer CKPT (a LocalizerNet checkpoint: a plain state_dict file, as the reference's load_facelocalizer reads
+                it, or {state_dict, class_name, config}) the face localizer runs on every frame and a lane that has been lost for
+                --reacquire-after frames (3) restarts from its box if the face probability exceeds --face-threshold (0.5); prints the
+                re-acquisitions per lane and writes g<g>/reacquired [C,T,L], g<g>/hasface [C,T], g<g>/loc_roi [C,T,4].
   open-loop     `Predictor.evaluate` with the stored boxes, per factor (:267-272).
   noise-resist  crops once with the predictor's own crop, adds N(0, (level / 256)^2) noise for the levels 0, 2, 8, 16, 32, 48, 64 from a
                 seeded device generator (--seed) and prints the mean geodesic error in degrees per level and checkpoint, with average and
@@ -86,15 +90,21 @@ class _Collect:
 
 def track_closed_loop(net, shard, args):
     frames = torch.from_numpy(shard["image"][:, 0])
-    out = E.ClosedLoopTracker(net, factors=args.factors, device=args.device, graphed=args.graphed).track(frames, shard["roi"][:1])
-    return poses_of(out["pose"].cpu().numpy(), out["coord"].cpu().numpy()), out["lost"].cpu().numpy()
+    localizer = models.load_localizer(args.localizer) if args.localizer else None
+    out = E.ClosedLoopTracker(net, factors=args.factors, device=args.device, graphed=args.graphed, localizer=localizer,
+                              reacquire_after=args.reacquire_after, face_threshold=args.face_threshold).track(frames, shard["roi"][:1])
+    extra = {k: out[k].cpu().numpy() for k in ("reacquired", "hasface", "loc_roi") if k in out}
+    for k in ("hasface", "loc_roi"):  # one video: [T, 1(, 4)] -> [T(, 4)]
+        if k in extra:
+            extra[k] = extra[k][:, 0]
+    return poses_of(out["pose"].cpu().numpy(), out["coord"].cpu().numpy()), out["lost"].cpu().numpy(), extra
 
 
 def track_open_loop(net, shard, args):
     samples = [{"image": torch.from_numpy(im[0]), "roi": torch.from_numpy(r)} for im, r in zip(shard["image"], shard["roi"])]
     runs = [E.Predictor(net, focus_roi_expansion_factor=f, device=args.device).evaluate(_Collect(), samples) for f in args.factors]
     poses = poses_of(np.stack([p for p, _ in runs], 1), np.stack([c for _, c in runs], 1))
-    return poses, np.zeros(poses["sz"].shape, dtype=bool)
+    return poses, np.zeros(poses["sz"].shape, dtype=bool), {}
 
 
 def run_tracking(args, shard, tracker) -> dict:
@@ -111,15 +121,19 @@ def run_tracking(args, shard, tracker) -> dict:
         print(f"Evaluating {path}. Found {len(files)} checkpoints.")
         runs = [tracker(models.load_model(f).to(args.device).eval(), shard, args) for f in files]
         for k in ("hpb", "xy", "sz"):
-            stack = [poses[k] for poses, _ in runs]
+            stack = [poses[k] for poses, _, _ in runs]
             saved[f"g{g}/{k}"], saved[f"g{g}/{k}_std"] = np.average(stack, axis=0), np.std(stack, axis=0)
-        saved[f"g{g}/lost"] = np.stack([lost for _, lost in runs])
-        for f, (_, lost) in zip(files, runs):
+        saved[f"g{g}/lost"] = np.stack([lost for _, lost, _ in runs])
+        for k in runs[0][2]:
+            saved[f"g{g}/{k}"] = np.stack([extra[k] for _, _, extra in runs])
+        for f, (_, lost, extra) in zip(files, runs):
             print(f"  {f}: lost frames per lane (factors {list(args.factors)}): {lost.sum(0).tolist()} of {lost.shape[0]}")
+            if "reacquired" in extra:
+                print(f"  {f}: re-acquisitions per lane: {extra['reacquired'].sum(0).tolist()}")
         if args.blinks:
             print(f"Checkpoint: {path}")
             for k in ("hpb", "sz", "xy"):  # the reference's order; a run = one checkpoint with one factor
-                per_run = [E.blink_stability(poses[k][:, lane], args.blinks) for poses, _ in runs for lane in range(len(args.factors))]
+                per_run = [E.blink_stability(poses[k][:, lane], args.blinks) for poses, _, _ in runs for lane in range(len(args.factors))]
                 val = np.average(per_run, axis=0) * (utils.rad2deg if k == "hpb" else 1.0)
                 print(f"\t {k:4s}: " + ", ".join(f"{x:0.2f}" for x in val))
     if args.output:
@@ -172,6 +186,9 @@ def make_parser():
     ap.add_argument("--blinks", type=parse_blinks, default=None, metavar="a:b,c:d", help="frame ranges with closed eyes: prints the blink-stability report")
     ap.add_argument("--output", type=str, default=None, help="the .npz to write")
     ap.add_argument("--graphed", action="store_true", default=False, help="closed-loop: replay one captured graph per frame")
+    ap.add_argument("--localizer", type=str, default=None, metavar="CKPT", help="closed-loop: a LocalizerNet checkpoint; lost lanes restart from its box")
+    ap.add_argument("--reacquire-after", type=int, default=3, help="closed-loop with --localizer: lost frames before a lane restarts")
+    ap.add_argument("--face-threshold", type=float, default=0.5, help="closed-loop with --localizer: face probability a restart needs")
     ap.add_argument("--seed", type=int, default=0, help="noise-resist: seed of the device generator")
     ap.add_argument("--device", default="cuda", type=str)
     return ap
@@ -183,6 +200,11 @@ def main(argv=None):
         raise SystemExit(f"mode {args.mode!r} is not built: {REFUSED[args.mode]}")
     if args.mode not in ("closed-loop", "open-loop", "noise-resist"):
         raise SystemExit(f"unknown mode {args.mode!r}: closed-loop, open-loop or noise-resist")
+    if args.localizer and args.mode != "closed-loop":
+        raise SystemExit(f"--localizer: mode {args.mode!r} crops every frame around a stored box and has no track to lose; the localizer "
+                         "re-acquires lost lanes of closed-loop only")
+    if args.localizer and not os.path.isfile(args.localizer):
+        raise SystemExit(f"--localizer: no such file {args.localizer!r}")
     shard = decode_pose_shard(args.data)
     if args.mode == "noise-resist":
         return run_noise_resist(args, shard)

@@ -11,6 +11,7 @@ What the reference's script does, and what is built here:
                                      folding, dynamic batch axis for the complete model) -> onnx shape inference,
                                      onnxsim, checker, model_version 4, optional fp16 -> onnxruntime comparison     see below
   quantize_backbone        :53-113   torch.ao post-training quantisation over 20 training batches                  NOT built
+  convert_localizer        :282-317  the face localizer: flush -> eval -> export(opset 12, input x, output logit_box)   built, see below
 
 This image has no `onnx` / `onnxsim` / `onnxruntime`, so `torch.onnx.export` cannot serialise.  `convert_posemodel_onnx` therefore
 runs everything up to the serialisation - flush, wrapper, the plain-torch CPU eval path of the HIP network (optionally with every
@@ -218,6 +219,50 @@ def convert_posemodel_onnx(net: nn.Module, filename, for_opentrack=True, quantiz
     return contract
 
 
+LOCALIZER_OPSET_VERSION = 12  # reference :303
+
+
+@torch.no_grad()
+def convert_localizer(net: nn.Module, filename, check_tol=1.0e-5):
+    """The face localizer (reference :282-317, up to the serialisation): denormal flush, eval(), `torch.jit.trace` on the CPU with a
+    [1, 1, 224, 288] input, checked against the eager module; writes `<name>.pt` + `<name>.contract.json` (input `x`, output
+    `logit_box`).  With `onnx` importable the function goes on to `torch.onnx.export` with the reference's arguments."""
+    net = net.to("cpu")
+    net.load_state_dict(clear_denormals(net.state_dict()), strict=True)
+    net.eval()
+    H, W = net.input_resolution
+    x = torch.randn(1, 1, H, W)
+    eager = net(x)
+    traced = torch.jit.trace(net, (x,), check_trace=False)
+    worst = float((traced(x) - eager).abs().max()) / max(float(eager.abs().max()), 1.0)
+    if worst > check_tol:
+        raise RuntimeError(f"the traced localizer differs from the eager module by {worst:.2e}")
+    contract = {
+        "doc_string": "Face localizer", "opset_version": LOCALIZER_OPSET_VERSION,
+        "inputs": [{"name": "x", "shape": list(x.shape), "dtype": "float32"}],
+        "outputs": [{"name": "logit_box", "shape": list(eager.shape), "dtype": "float32"}],
+        "dynamic_axes": None, "max_rel_delta_traced_vs_eager": worst,
+    }
+    try:
+        import onnx  # noqa: F401
+        have_onnx = True
+    except ImportError:
+        have_onnx = False
+    if have_onnx:  # the reference's call (:290-306); never reached in this image
+        destination = splitext(filename)[0] + ".onnx"
+        torch.onnx.export(net, x, destination, export_params=True, opset_version=LOCALIZER_OPSET_VERSION, do_constant_folding=True, input_names=["x"], output_names=["logit_box"],
+                          verbose=False)
+        onnx.checker.check_model(onnx.load(destination))
+    else:
+        destination = splitext(filename)[0] + ".pt"
+        print(f"`onnx` is not installed: writing the traced graph {destination} and its contract instead of an .onnx file")
+        traced.save(destination)
+    contract["file"] = destination
+    with open(splitext(destination)[0] + ".contract.json", "w") as fh:
+        json.dump(contract, fh, indent=1)
+    return contract
+
+
 class _ExportLike(nn.Module):
     """ExportModel over an already-probed list of output names (the folded network has the same outputs as the original)."""
 
@@ -239,7 +284,8 @@ def main():
     parser.add_argument("--fp16", action="store_true", default=False)
     args = parser.parse_args()
     if args.localizermodelfilename:
-        raise NotImplementedError("the face localizer network (reference :172-176, 282-324) is outside the pose-estimator path (SURVEY.md §2)")
+        net = trackertraincode.neuralnets.models.load_localizer(args.localizermodelfilename)
+        print(json.dumps(convert_localizer(net, args.localizermodelfilename), indent=1))
     if args.posemodelfilename:
         net = trackertraincode.neuralnets.models.load_model(args.posemodelfilename)
         contract = convert_posemodel_onnx(net, args.posemodelfilename, for_opentrack=not args.full, quantize=args.quantize, fp16=args.fp16)

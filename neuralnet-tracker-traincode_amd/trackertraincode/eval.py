@@ -132,6 +132,56 @@ class Predictor:
 
 
 # ---------------------------------------------------------------------------------------------
+# the face localizer (reference: neuralnets/models.py LocalizerNet; the reference tree holds no code that maps its boxes to pixels)
+# ---------------------------------------------------------------------------------------------
+class Localizer:
+    """The face localizer on whole frames: `localize(frames)` takes uint8 or float32 grey-level frames [B, H, W] of any one size and
+    returns a Batch with logit [B], hasface [B] (the sigmoid of the logit), roi [B, 4] in frame pixels, roi_normalized [B, 4] (the
+    network's own box in the input's [-1, 1] coordinates) and letterbox [B, 3] = (s, ox, oy).  One ttk_localizer_input (letterbox into 224 x 288: uniform scale
+    s = min(288 / W, 224 / H), centred with offsets ox, oy, exact area averages, outside the frame grey level 0, whitened like the pose
+    crops) plus one LocalizerNet forward (csrc/localizer.hip); nothing is read on the host.
+
+    The map from the network's box to pixels is THIS PROJECT'S convention - the reference tree has none: input pixels
+    X = (x + 1) * 144, Y = (y + 1) * 112, frame pixels ((X - ox) / s, (Y - oy) / s); ttk_track_reacquire (csrc/localizer_math.h) rounds
+    the same float32 steps."""
+
+    MUL, ADD = 1.0 / 256.0, -0.5  # whitening of GpuFocusRoiAugment, as the pose crops
+
+    def __init__(self, net: torch.nn.Module, device: str | torch.device = "cuda", threshold: float = 0.5):
+        self._net = net.to(device).eval()
+        self._device = torch.device(device)
+        self.threshold = float(threshold)
+
+    def run(self, frames: Tensor, t_dev: Tensor | None = None):
+        """frames [S, T, H, W] on the device, contiguous; frame *t_dev of every sequence (None: frame 0) -> (out [S, 5], lb [S, 3] =
+        (s, ox, oy)).  Enqueues only."""
+        S, T, Hs, Ws = (int(v) for v in frames.shape)
+        H, W = self._net.input_resolution
+        x = torch.empty((S, 1, H, W), dtype=torch.float32, device=frames.device)
+        lb = torch.empty((S, 3), dtype=torch.float32, device=frames.device)
+        _hip.lib().call("ttk_localizer_input", _hip.fast_ptr(frames), int(frames.dtype == torch.uint8), S, T, Hs, Ws, _hip.fast_ptr(t_dev),
+                        self.MUL, self.ADD, _hip.fast_ptr(x), _hip.fast_ptr(lb))
+        return self._net(x), lb
+
+    @staticmethod
+    def to_frame_pixels(box: Tensor, lb: Tensor) -> Tensor:
+        """box [B, 4] in [-1, 1], lb [B, 3] = (s, ox, oy) -> frame pixels, every float32 step rounded on its own."""
+        half = box.new_tensor([144.0, 112.0, 144.0, 112.0])
+        return ((box + 1.0) * half - lb[:, [1, 2, 1, 2]]) / lb[:, :1]
+
+    @torch.no_grad()
+    def localize(self, frames) -> Batch:
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 3 or frames.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"Localizer.localize: frames are uint8 or float32 [B, H, W], got {frames.dtype} {tuple(frames.shape)}")
+        _hip.lib().clear_stale_error("the start of a localizer batch")
+        out, lb = self.run(frames.to(self._device).contiguous()[:, None])
+        data = {"logit": out[:, 0], "hasface": torch.sigmoid(out[:, 0]), "roi": self.to_frame_pixels(out[:, 1:], lb),
+                "roi_normalized": out[:, 1:], "letterbox": lb}
+        return Batch(Metadata((int(frames.shape[2]), int(frames.shape[1])), int(frames.shape[0]), categories={"roi": FieldCategory.roi}), data)
+
+
+# ---------------------------------------------------------------------------------------------
 # closed-loop tracking (reference: scripts/evaluate_stability.py:229-264)
 # ---------------------------------------------------------------------------------------------
 TRACK_MAX_LANES = 16  # kTrackMaxLanes of csrc/track.hip
@@ -169,11 +219,19 @@ class ClosedLoopTracker:
     Not in closed loop: area-filtered resampling (ttk_area_crop has no fused form: `resample="area"` is refused) and the uncertainty
     outputs (`pose_scales_tril`, `coord_scales`), which are not recorded.
 
+    `localizer` (a LocalizerNet; default None: the launches and the bits above): the face localizer runs on frame t of every sequence
+    inside the same loop - ttk_localizer_input + its forward before the update, ttk_track_reacquire after it, all on one stream - and a
+    lane that has been lost for `reacquire_after` frames restarts from the localizer's box, clamped to the image, if that box is valid by
+    the rule above and the face probability exceeds `face_threshold`.  The localizer runs on every frame, needed or not: that keeps the
+    loop free of host reads.  The Batch gains reacquired [T,L] (bool), hasface [T,S], loc_roi [T,S,4] (frame pixels, `Localizer`'s
+    convention), and `first_rois` may be omitted: frame 0 of every sequence is localized once before the loop (one host read), and a
+    sequence without a valid box above the threshold raises ValueError.
+
     graphed=True captures crop -> forward -> update once (after a warm-up frame on scratch state) and replays the graph T times; the
     device counter selects the frame.  A single-stream, linear graph; bitwise the eager trajectory."""
 
     def __init__(self, net: torch.nn.Module, factors=(1.0, 1.2), device: str | torch.device = "cuda", graphed: bool = False,
-                 resample: str = "bilinear"):
+                 resample: str = "bilinear", localizer: torch.nn.Module | None = None, reacquire_after: int = 3, face_threshold: float = 0.5):
         if resample != "bilinear":
             raise ValueError(f"ClosedLoopTracker: resample={resample!r} is not available in closed loop - the fused crop (ttk_track_crop) "
                              "samples bilinearly; ttk_area_crop takes a host-side image base pointer and has no fused form")
@@ -182,6 +240,10 @@ class ClosedLoopTracker:
         self._factors = tuple(float(f) for f in factors)
         self._graphed = bool(graphed)
         self._mul, self._add = 1.0 / 256.0, -0.5  # whitening of GpuFocusRoiAugment, as Predictor crops
+        if int(reacquire_after) < 1:
+            raise ValueError(f"ClosedLoopTracker: reacquire_after counts lost frames, at least 1, got {reacquire_after}")
+        self._localizer = None if localizer is None else Localizer(localizer, device, face_threshold)
+        self._reacquire_after, self._face_threshold = int(reacquire_after), float(face_threshold)
 
     @property
     def input_resolution(self) -> int:
@@ -202,11 +264,33 @@ class ClosedLoopTracker:
         st["keep"] = outs = [preds[k].to(torch.float32).contiguous() for k in ("roi", "coord", "pose")]
         pts = preds["pt3d_68"].to(torch.float32).contiguous() if st["traj_pts"] is not None else None
         outs.append(pts)
+        if self._localizer is not None:  # on frame t of every sequence, before the update advances the counter; the same stream
+            loc_out, lb = self._localizer.run(st["frames"], st["t"])
+            outs += [loc_out, lb]
         call("ttk_track_update", P(outs[0]), P(outs[1]), P(outs[2]), P(pts), P(st["tr"]), P(st["t"]), L, N, T, Hs, Ws, P(st["lane_factor"]),
              P(st["roi_state"]), P(st["roi_in"]), P(st["roi"]), P(st["coord"]), P(st["pose"]), P(st["traj_pts"]), P(st["lost"]))
+        if self._localizer is not None:
+            call("ttk_track_reacquire", P(loc_out), P(lb), P(st["t"]), L, S, T, Hs, Ws, P(st["lane_seq"]), P(st["lane_factor"]), P(st["lost"]),
+                 self._reacquire_after, self._face_threshold, P(st["roi_state"]), P(st["lost_run"]), P(st["reacquired"]), P(st["hasface"]),
+                 P(st["loc_roi"]))
+
+    def _first_boxes(self, frames: Tensor, lanes) -> Tensor:
+        """Frame 0 of every sequence through the localizer: the start boxes [S, 4] (clamped to the image) on the host - the one host
+        read before the loop.  A sequence without a valid box above the threshold raises."""
+        S, _, Hs, Ws = frames.shape
+        out, lb = self._localizer.run(frames, None)
+        roi, hasface = Localizer.to_frame_pixels(out[:, 1:], lb).cpu(), torch.sigmoid(out[:, 0]).cpu()
+        first = torch.stack([roi[:, 0].clamp(min=0.0), roi[:, 1].clamp(min=0.0), roi[:, 2].clamp(max=float(Ws)), roi[:, 3].clamp(max=float(Hs))], dim=1)
+        for q in range(S):
+            factors = [f for s_, f in lanes if s_ == q] or [1.0]
+            ok = bool(torch.isfinite(roi[q]).all()) and all(track_box_is_valid(first[q].numpy(), f, Ws, Hs) for f in factors)
+            if not (ok and float(hasface[q]) > self._face_threshold):
+                raise ValueError(f"ClosedLoopTracker.track: the localizer finds no face to start from in frame 0 of sequence {q} "
+                                 f"(box {roi[q].tolist()}, face probability {float(hasface[q]):.3f}, threshold {self._face_threshold})")
+        return first
 
     @torch.no_grad()
-    def track(self, frames, first_rois, lanes=None) -> Batch:
+    def track(self, frames, first_rois=None, lanes=None) -> Batch:
         dev = self._device
         frames = torch.as_tensor(frames)
         if frames.dim() == 3:
@@ -214,15 +298,24 @@ class ClosedLoopTracker:
         if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32):
             raise ValueError(f"ClosedLoopTracker.track: frames are uint8 or float32 [T,H,W] or [S,T,H,W], got {frames.dtype} {tuple(frames.shape)}")
         S, T, Hs, Ws = (int(v) for v in frames.shape)
-        first = torch.as_tensor(first_rois, dtype=torch.float32).reshape(-1, 4).cpu()
-        if first.shape[0] != S:
-            raise ValueError(f"ClosedLoopTracker.track: first_rois has {first.shape[0]} boxes for {S} sequences")
+        if first_rois is None and self._localizer is None:
+            raise ValueError("ClosedLoopTracker.track: without a localizer the box of frame 0 of every sequence is needed (first_rois)")
+        if first_rois is not None:
+            first = torch.as_tensor(first_rois, dtype=torch.float32).reshape(-1, 4).cpu()
+            if first.shape[0] != S:
+                raise ValueError(f"ClosedLoopTracker.track: first_rois has {first.shape[0]} boxes for {S} sequences")
         if lanes is None:
             lanes = [(s, f) for s in range(S) for f in self._factors]
         lanes = [(int(s), float(f)) for s, f in lanes]
         L = len(lanes)
         if not 1 <= L <= TRACK_MAX_LANES:
             raise ValueError(f"ClosedLoopTracker.track: 1 to {TRACK_MAX_LANES} lanes (sequence x factor), got {L}")
+        frames = frames.to(dev).contiguous()
+        if first_rois is None:  # frame 0 of every sequence through the localizer: the one host read before the loop
+            if T < 1:
+                raise ValueError("ClosedLoopTracker.track: no frames")
+            _hip.lib().clear_stale_error("the start of a closed-loop track")
+            first = self._first_boxes(frames, [(s, f) for s, f in lanes if 0 <= s < S])
         for i, (s, f) in enumerate(lanes):
             if not 0 <= s < S:
                 raise ValueError(f"ClosedLoopTracker.track: lane {i} follows sequence {s}, but there are {S}")
@@ -238,12 +331,15 @@ class ClosedLoopTracker:
         lane_factor = torch.tensor([f for _, f in lanes], **f32)
         start = first[[s for s, _ in lanes]].to(dev).contiguous()
         with_pts = bool(getattr(self._net, "enable_point_head", False))
-        st = {"L": L, "N": N, "frames": frames.to(dev).contiguous(), "u8": int(frames.dtype == torch.uint8), "lane_seq": lane_seq,
+        st = {"L": L, "N": N, "frames": frames, "u8": int(frames.dtype == torch.uint8), "lane_seq": lane_seq,
               "lane_factor": lane_factor, "roi_state": start.clone(), "t": torch.zeros((), dtype=torch.int32, device=dev),
               "view": torch.empty((L, 4), dtype=torch.int32, device=dev), "tr": torch.empty((L, 2, 3), **f32),
               "crop": torch.empty((L, 1, N, N), **f32), "roi_in": torch.zeros((T, L, 4), **f32), "roi": torch.zeros((T, L, 4), **f32),
               "coord": torch.zeros((T, L, 3), **f32), "pose": torch.zeros((T, L, 4), **f32),
               "traj_pts": torch.zeros((T, L, 68, 3), **f32) if with_pts else None, "lost": torch.zeros((T, L), dtype=torch.uint8, device=dev)}
+        if self._localizer is not None:
+            st.update(lost_run=torch.zeros((L,), dtype=torch.int32, device=dev), reacquired=torch.zeros((T, L), dtype=torch.uint8, device=dev),
+                      hasface=torch.zeros((T, S), **f32), loc_roi=torch.zeros((T, S, 4), **f32))
         if self._graphed:
             self._replay(st, start, T)
         else:
@@ -256,6 +352,8 @@ class ClosedLoopTracker:
                "lane_seq": lane_seq, "lane_factor": lane_factor}
         if with_pts:
             out["pt3d_68"] = st["traj_pts"]
+        if self._localizer is not None:
+            out.update(reacquired=st["reacquired"].bool(), hasface=st["hasface"], loc_roi=st["loc_roi"])
         cats = {"coord": FieldCategory.xys, "pose": FieldCategory.quat, "pt3d_68": FieldCategory.points, "roi": FieldCategory.roi,
                 "roi_in": FieldCategory.roi}
         return Batch(Metadata(N, T, categories={k: c for k, c in cats.items() if k in out}), out)
@@ -269,6 +367,8 @@ class ClosedLoopTracker:
                 self._frame(st)
                 st["roi_state"].copy_(start)
                 st["t"].zero_()
+                if self._localizer is not None:
+                    st["lost_run"].zero_()
             torch.cuda.current_stream(self._device).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):

@@ -108,6 +108,39 @@ class PosedDeformableHead(nn.Module):
         return rigid_transformation_25d(rots, coord[..., :2], coord[..., 2:], self.deformable_head(params))
 
 
+class CenterOfMass(nn.Module):
+    """Expected position under a spatial probability map x [B, H, W] (reference :98-119): the map's mean over a position code that runs
+    from -1 to 1 along either axis, end points included, times the parameter `half_size`.  `position_code` [2, H, W] (x, then y) is
+    set by forward() and is float32 whatever the map's type, as in the reference."""
+
+    def __init__(self, half_size=1.0):
+        super().__init__()
+        self.half_size = nn.Parameter(torch.tensor(half_size, requires_grad=True, dtype=torch.float32))
+        self.position_code: Optional[Tensor] = None
+
+    def forward(self, x):
+        _, H, W = x.shape
+        code = torch.empty((2, H, W), dtype=torch.float32, device=x.device, requires_grad=False)
+        code[0] = torch.linspace(-1.0, 1.0, W, device=x.device)[None, :]
+        code[1] = torch.linspace(-1.0, 1.0, H, device=x.device)[:, None]
+        self.position_code = code
+        return self.half_size * torch.sum(x[:, None] * code[None], dim=[2, 3])
+
+
+class CenterOfMassAndStd(CenterOfMass):
+    """(mean, deviation) of the map (reference :123-133).  Reference quirk kept as written: the deviation measures the UNSCALED position
+    code against the mean that `half_size` has already scaled."""
+
+    def __init__(self, eps=1.0e-4, half_size=1.0):
+        super().__init__(half_size)
+        self._eps = eps
+
+    def forward(self, x):
+        mean = super().forward(x)
+        d = self.position_code[None] - mean[..., None, None]
+        return mean, torch.sqrt(torch.sum(x[:, None] * (d * d), dim=[2, 3]) + self._eps)
+
+
 class LocalToGlobalCoordinateOffset(nn.Module):
     """Per-dataset correction of the predicted pose: rotation about x, translation in the head frame and
     a scale factor, one row of `p` per dataset id (reference :136-184).

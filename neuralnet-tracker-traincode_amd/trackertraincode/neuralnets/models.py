@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from .. import _hip
 from . import _hipops
 from . import io as _io
 from . import negloglikelihood as NLL
@@ -22,6 +23,7 @@ from . import torchquaternion
 from ..backbones.mobilenet_v1 import MobileNet
 from .math import inv_smoothclip0, smoothclip0
 from .modelcomponents import (
+    CenterOfMassAndStd,
     DeformableHeadKeypoints,
     LocalToGlobalCoordinateOffset,
     freeze_norm_stats,
@@ -313,6 +315,133 @@ class NetworkWithPointHead(nn.Module):
             # backbone then runs its backward through the fixed affine maps (ttk_bn_bwd_frozen)
             self.convnet.apply(freeze_norm_stats)
         return self
+
+
+# ---------------------------------------------------------------------------------------------
+# the face localizer (reference :30-93): the tracker's first network, which finds the face box in the whole frame
+# ---------------------------------------------------------------------------------------------
+class _InvertedResidual(nn.Module):
+    """torchvision's `mnasnet._InvertedResidual` restated (the package is not a dependency) with its attribute names, so that state
+    dicts interchange: `layers` = conv 1x1, BN, ReLU, depthwise k x k (stride, padding k // 2), BN, ReLU, conv 1x1, BN; the input is
+    added when `apply_residual` (in_ch == out_ch and stride == 1)."""
+
+    def __init__(self, in_ch, out_ch, kernel_size, stride, expansion_factor, bn_momentum=0.1):
+        super().__init__()
+        assert stride in (1, 2) and kernel_size in (3, 5)
+        mid = in_ch * expansion_factor
+        self.apply_residual = in_ch == out_ch and stride == 1
+        self.layers = nn.Sequential(
+            nn.Conv2d(in_ch, mid, 1, bias=False), nn.BatchNorm2d(mid, momentum=bn_momentum), nn.ReLU(inplace=True),
+            nn.Conv2d(mid, mid, kernel_size, padding=kernel_size // 2, stride=stride, groups=mid, bias=False),
+            nn.BatchNorm2d(mid, momentum=bn_momentum), nn.ReLU(inplace=True),
+            nn.Conv2d(mid, out_ch, 1, bias=False), nn.BatchNorm2d(out_ch, momentum=bn_momentum))
+
+    def forward(self, x):
+        return self.layers(x) + x if self.apply_residual else self.layers(x)
+
+
+def _fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
+    """(w', b') of the convolution with its eval-mode BatchNorm folded in, in float64: w' = w g / sqrt(var + eps), b' = beta - mean g /
+    sqrt(var + eps)."""
+    g = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    w = conv.weight.detach().double() * g[:, None, None, None]
+    return w.reshape(w.shape[0], -1), bn.bias.detach().double() - bn.running_mean.detach().double() * g
+
+
+class LocalizerNet(nn.Module):
+    """x [B, 1, 224, 288] (whitened grey levels) -> [B, 5] = (face logit, x0, y0, x1, y1), the box in the input's [-1, 1] coordinates;
+    `attentionmap` [B, 7, 9] is set by forward().  Module tree and state dict are the reference's (`initial_stage.*` appears a second
+    time as `convnet.0.*`).  CPU tensors run plain torch ops in either mode (inspection / export); CUDA tensors in eval() run the HIP
+    path (csrc/localizer.hip: ttk_localizer_forward over BatchNorm-folded parameters, packed once per parameter version); training on
+    the device is not built."""
+
+    # (in_ch, out_ch, kernel, stride, expansion) of convnet[2:14]; ttk_localizer_forward's block table (csrc/localizer.hip) is the same
+    BLOCKS = ((8, 12, 3, 2, 2), (12, 12, 3, 1, 2), (12, 20, 3, 2, 4), (20, 20, 3, 1, 4), (20, 20, 3, 1, 4), (20, 32, 5, 2, 2),
+              (32, 32, 5, 1, 2), (32, 32, 3, 1, 2), (32, 32, 3, 1, 2), (32, 56, 3, 2, 2), (56, 56, 3, 1, 2), (56, 56, 3, 1, 2))
+
+    def __init__(self):
+        super().__init__()
+        self.input_resolution = (224, 288)  # H x W
+        self.initial_stage = nn.Sequential(nn.Conv2d(1, 8, 3, padding=1, stride=2, bias=False), nn.BatchNorm2d(8), nn.ReLU())
+        first_pair = nn.Sequential(nn.Conv2d(8, 8, 3, groups=8, bias=False, padding=1), nn.BatchNorm2d(8, momentum=0.001), nn.ReLU(inplace=True),
+                                   nn.Conv2d(8, 8, 1, bias=False), nn.BatchNorm2d(8, momentum=0.001))
+        self.convnet = nn.Sequential(self.initial_stage, first_pair,
+                                     *[_InvertedResidual(i, o, kernel_size=k, stride=s, expansion_factor=e) for i, o, k, s, e in self.BLOCKS],
+                                     nn.Conv2d(56, 2, 1, bias=True))
+        self.boxstddev = CenterOfMassAndStd(half_size=1.5)
+        self._packed = None  # (key, float32 device tensor): the parameter block of ttk_localizer_forward
+
+    def packed_parameters(self, device) -> Tensor:
+        """The parameter block of ttk_localizer_forward (layout: include/ttk.h) on `device`: every BatchNorm folded into its convolution
+        in float64, rounded once to float32.  Packed again only when a parameter or buffer has changed (tensor versions)."""
+        device = torch.device(device)
+        state = list(self.parameters()) + list(self.buffers())
+        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in state)
+        if self._packed is None or self._packed[0] != key:
+            parts = []
+            for conv, bn in ((self.initial_stage[0], self.initial_stage[1]), (self.convnet[1][0], self.convnet[1][1]), (self.convnet[1][3], self.convnet[1][4])):
+                parts += _fold_bn(conv, bn)
+            for blk in list(self.convnet)[2:14]:
+                for c in (0, 3, 6):
+                    parts += _fold_bn(blk.layers[c], blk.layers[c + 1])
+            last = self.convnet[14]
+            parts += [last.weight.detach().double().reshape(2, 56), last.bias.detach().double(),
+                      self.boxstddev.half_size.detach().double().reshape(1), torch.tensor([self.boxstddev._eps], dtype=torch.float64)]
+            block = torch.cat([p.reshape(-1).cpu() for p in parts]).to(torch.float32)
+            n = _hip.lib().cdll.ttk_localizer_param_floats()
+            assert block.numel() == n, (block.numel(), n)
+            self._packed = (key, block.to(device))
+        return self._packed[1]
+
+    def _forward_hip(self, x: Tensor) -> Tensor:
+        lib = _hip.lib()
+        B = int(x.shape[0])
+        x = x.to(torch.float32).contiguous()
+        params = self.packed_parameters(x.device)
+        ws = torch.empty(lib.cdll.ttk_localizer_workspace_bytes(B), dtype=torch.uint8, device=x.device)
+        out = torch.empty((B, 5), dtype=torch.float32, device=x.device)
+        att = torch.empty((B, 7, 9), dtype=torch.float32, device=x.device)
+        lib.call("ttk_localizer_forward", x.data_ptr(), params.data_ptr(), ws.data_ptr(), B, out.data_ptr(), att.data_ptr())
+        self.attentionmap = att
+        return out
+
+    def forward(self, x):
+        assert x.shape[1] == 1 and tuple(x.shape[2:]) == self.input_resolution
+        if x.is_cuda:
+            if self.training:
+                raise NotImplementedError("LocalizerNet: training the localizer on the device is not built (only its inference path is: "
+                                          "call eval(); CPU tensors run plain torch ops in either mode)")
+            with torch.no_grad():
+                return self._forward_hip(x)
+        z = self.convnet(x)
+        logit = torch.mean(z[:, 0], dim=[1, 2])
+        m = z[:, 1]
+        m = torch.softmax(m.reshape(m.shape[0], -1), dim=1).view(*m.shape)
+        self.attentionmap = m
+        mean, std = self.boxstddev(m)
+        pred = m.new_empty((m.shape[0], 5))
+        pred[:, 0] = logit
+        pred[:, 1:3] = mean - std
+        pred[:, 3:5] = mean + std
+        return pred
+
+    def inference(self, x):
+        assert not self.training
+        pred = self.forward(x)
+        return {"hasface": torch.sigmoid(pred[:, 0]), "roi": pred[:, 1:]}
+
+
+def load_localizer(filename: str) -> LocalizerNet:
+    """A localizer checkpoint: a plain `state_dict` file (what the reference's `load_facelocalizer` reads) or {state_dict, class_name,
+    config} as `save_model` writes it."""
+    blob = torch.load(filename, map_location="cpu")
+    if isinstance(blob, dict) and "state_dict" in blob and isinstance(blob["state_dict"], dict):
+        if blob.get("class_name", "LocalizerNet") != "LocalizerNet":
+            raise ValueError(f"{filename} holds a {blob['class_name']}, not a LocalizerNet")
+        blob = blob["state_dict"]
+    net = LocalizerNet()
+    net.load_state_dict(blob, strict=True)
+    return net.eval()
 
 
 save_model = _io.save_model
