@@ -382,6 +382,10 @@ int ttk_stem_bwd_weight(const void* g, const void* y, const float* bn, const flo
                         int B, int H, int W, int act_bf16, ttk_stream_t stream) {
   TTK_REQUIRE(g && y && bn && x && dw, "stem_bwd_weight: null pointer");
   TTK_REQUIRE(B > 0 && H > 4 && W > 4, "stem_bwd_weight: bad shape");
+  // every refusal comes before the first launch: a refused call leaves dw as it was
+  TTK_REQUIRE((act_bf16 & 3) == 0 || (act_bf16 & 3) == 3, "the stem takes fp32 tensors or activations AND gradients bfloat16 (bf16-compute path)");
+  const size_t sm = ((size_t)(2 * kWgBand + 3) * W + (kBlock / kWave) * (kWgChunk * kStemC + kStemC * 25)) * sizeof(float);
+  TTK_REQUIRE(sm <= 64 * 1024, "stem_bwd_weight: image too wide for the LDS band (W=%d)", W);
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   if (!accumulate && !partial) hipLaunchKernelGGL(zero_k, dim3(4), dim3(256), 0, (hipStream_t)stream, dw, 25 * kStemC);
   // three workgroups fit a CU (44 KB of LDS each): 768 persistent workgroups are all resident - with 1 024 the last quarter only
@@ -390,8 +394,6 @@ int ttk_stem_bwd_weight(const void* g, const void* y, const float* bn, const flo
   const int band_rows = stem_band_rows(B, Ho, resident, kWgBand);
   const int nbands = (Ho + band_rows - 1) / band_rows;
   const int grid = B * nbands < resident ? B * nbands : resident;
-  const size_t sm = ((size_t)(2 * kWgBand + 3) * W + (kBlock / kWave) * (kWgChunk * kStemC + kStemC * 25)) * sizeof(float);
-  TTK_REQUIRE(sm <= 64 * 1024, "stem_bwd_weight: image too wide for the LDS band (W=%d)", W);
   TTK_ACT_DISPATCH_STEM(act_bf16, hipLaunchKernelGGL((stem_wgrad_mfma_k<ActT, GradT>), dim3(grid), dim3(kBlock), sm, (hipStream_t)stream, (const GradT*)g,
                                                 (const ActT*)y, bn, x, dw, partial, B, H, W, Ho, Wo, nbands, band_rows));
   if (partial) launch_fold_partials(partial, grid, 25 * kStemC, dw, accumulate, (hipStream_t)stream);
