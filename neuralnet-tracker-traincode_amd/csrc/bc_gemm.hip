@@ -393,6 +393,16 @@ static bool pw_shape_ok(int Cin, int Cout) {
 // E: N <= 128 and K <= 256; else L needs N % 256 == 0 and K % 64 == 0
 static bool is_e(int K, int N) { return N <= 128 && K <= 256; }
 static bool is_l(int K, int N) { return N % 256 == 0 && K % 128 == 0; }
+// the instantiations of bc_gemm_e_k as (NB, KH) = (N / 32, K / 32): the ONE list that the query (ttk_bc_partial_rows_pw) and launch_gemm read -
+// the E domain holds more power-of-two shapes than kernels.  Forward 32 -> 64, 64 -> 128, 128 -> 128; data gradient of 32 -> 64, 64 -> 128
+// (and 4, 4: 128 -> 128); K = 256 runs the streamed kernel
+#define TTK_BC_E_LIST(X) X(2, 1) X(4, 2) X(4, 4) X(1, 2) X(2, 4)
+static bool e_has_kernel(int K, int N) {
+#define TTK_BC_E_HAS(NB_, KH_) if (N == 32 * NB_ && K == 32 * KH_) return true;
+  TTK_BC_E_LIST(TTK_BC_E_HAS)
+#undef TTK_BC_E_HAS
+  return false;
+}
 static bool is_l128(int K, int N) { return N == 128 && K == 256; }  // (K = 128, N = 128 - the 128 -> 128 forward - is faster in the resident-weight form: 68 vs 90 us)  // (takes precedence over the resident-weight form for this shape, in both modes: the part rows depend on it)
 
 struct LPlan { int RT, nrt, ncol, grid; };
@@ -442,8 +452,7 @@ static int launch_gemm(const bf16_t* A0, const bf16_t* A1, const float* bnA, con
     hipLaunchKernelGGL((bc_gemm_e_k<MODE, NB_, KH_>), dim3(grid), dim3(512), sm, st, A0, A1, bnA, Wimg, out, maskY, bnE, pivot, part, M);             \
     return 0;                                                                                                                                     \
   }
-    TTK_BC_E(2, 1) TTK_BC_E(4, 2) TTK_BC_E(4, 4)            // forward: 32 -> 64, 64 -> 128, 128 -> 128
-    TTK_BC_E(1, 2) TTK_BC_E(2, 4)                           // data gradient of 32 -> 64, 64 -> 128 (and 4, 4: 128 -> 128); K = 256 runs the streamed kernel
+    TTK_BC_E_LIST(TTK_BC_E)
 #undef TTK_BC_E
     return -2;
   }
@@ -488,7 +497,7 @@ int ttk_bc_prepare_weights(int n, const float* const* w, const int* cin, const i
 int ttk_bc_partial_rows_pw(int64_t M, int K, int Nout) {
   if (M < 1 || !pw_shape_ok(K, Nout)) return -1;
   if (is_l128(K, Nout)) return l_plan(M, Nout, 128).nrt;
-  if (is_e(K, Nout)) return e_grid(M);
+  if (is_e(K, Nout)) return e_has_kernel(K, Nout) ? e_grid(M) : -1;  // (64 -> 64, 32 -> 128, 32 -> 32: launch_gemm refuses them)
   if (is_l(K, Nout)) return l_plan(M, Nout).nrt;
   return -1;
 }
